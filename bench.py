@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: codes/sec tokenized (text+graph embeddings -> VQ token ids) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2] [--rows R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2] [--rows R] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2], the one the >= 600k codes/s target is quoted on): the full MedTok
 soft VQ -- per code 4 nearest-code searches (text / graph over their 16384-row codebook thirds, shared
@@ -10,11 +10,17 @@ on R = 600000 synthetic codes per GPU, D = 768, fp32, cross-attention pooling al
 A "step" is one pass of that path over the rank's R rows, inputs resident in HBM.  Rows are
 independent, so N GPUs run N row shards with no data-path collective ("weak" scaling: R per GPU).
 
-One JSON line on rank 0 (contract in the task statement) plus:
-  roofline      -- the dominant kernel (fp32-MFMA search) timed live with HIP events on its launch
-                   stream; achieved = algorithmic flops (2*rows*K*D per launch) / kernel time.
-  cpu_baseline  -- the reference's op sequence (oracle/torch_port.py, pinned to golden vectors) timed
-                   on this box's host cores on a bounded row sample of the same workload.
+A plain run sets up, warms up, times K steps and prints one JSON line on rank 0: metric, value (codes/s
+over the K timed steps), unit, higher_is_better, dtype, ms_per_step, the run's shape and config.
+  --dump-outputs DIR  what the last timed step returned, as DIR/<name>.npy (rank 0; see dump_outputs).
+  --full              everything else, measured after the timed region and added to the line:
+    roofline      -- the dominant kernel (fp32-MFMA search) timed live with HIP events on its launch
+                     stream; achieved = algorithmic flops (2*rows*K*D per launch) / kernel time.
+    cpu_baseline  -- the reference's op sequence (oracle/torch_port.py, pinned to golden vectors) timed
+                     on the host's cores on a bounded row sample of the same workload.
+    and the shader clock, the shortlist's fallback statistics, the exact fp32-MFMA path, the workloads'
+    extra passes, the short runs of the other workloads (default workload) and, for N > 1, the
+    strong-scaling block.
 """
 from __future__ import annotations
 
@@ -62,13 +68,22 @@ def parse():
                     help="full workload: skip the extra pass with fp16 text features (what a caller under fp16 autocast hands over)")
     ap.add_argument("--no-clock-probe", action="store_true", help="do not run the shader-clock probe beside the timed region")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="default run (cfg3, 1 GPU): skip the short runs of the other workloads appended as extra.workloads")
+                    help="--full on the default workload (cfg3, 1 GPU): skip the short runs of the other workloads appended as extra.workloads")
     ap.add_argument("--data", choices=["gaussian", "near_codes", "clustered_codebook", "heavy_tail"], default="gaussian",
                     help="cfg3 / refdefault: the synthetic distribution (BASELINE prescribes i.i.d. Gaussian rows and codes; the others probe the "
                          "shortlist's data-dependent cost: rows near codes, a codebook of near-copies, Student-t rows)")
     ap.add_argument("--no-one-stream-pass", action="store_true",
                     help="full workload: skip the second, one-stream pass that times the kernels for the roofline object (timeline captures)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and report everything beyond the headline (roofline, cpu_baseline, clock, "
+                         "exact path, extra passes and workloads, strong scaling); the --no-* / --cpu-rows / --exact-steps options apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all: a seeded row sample "
+                         "of larger outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def cpu_protocol(run, rows_full, unit_rows, what):
@@ -104,6 +119,7 @@ class Cfg3:
     name = "cfg3"
     D, REGION, TOPK = 768, 16384, 5
     N_E = 3 * REGION
+    OUTPUTS = ("embedding", "tokens", "weights")          # step()'s tuple (quantize_pooled); Full's step returns a dict
 
     def __init__(self, rows, dev, seed, path, data="gaussian"):
         from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer
@@ -408,6 +424,7 @@ class CodeShard:
     rank's slice (HIP search) -> all-gather of (distance, global id) lists over RCCL -> exact merge -> soft assignment."""
     name = "codeshard"
     D, K, TOPK = 768, 49152, 5
+    OUTPUTS = ("idx", "dist", "w", "zq")
 
     def __init__(self, rows, dev, seed, path, rank, world):
         self.rows, self.dev, self.path = rows, dev, path
@@ -458,6 +475,7 @@ class Cfg2:
     """Single-modality argmin + EMA train step (NormEMAVectorQuantizer), K = 8192."""
     name = "cfg2"
     D, K = 768, 8192
+    OUTPUTS = ("zq", "loss", "idx")
 
     def __init__(self, rows, dev, seed, path, k_codes=None):
         if k_codes:
@@ -516,6 +534,7 @@ class Cfg4:
     GAT): they are upstream of the path this package rebuilds, so their time is reported separately (`encoders_ms_per_step`)."""
     name = "cfg4"
     D, N_E, L, TOPK = 768, 49152, 512, 5
+    OUTPUTS = ("loss",)
 
     def __init__(self, rows, dev, seed, path, text_layers=12, precomputed=False):
         from medtok_amd.synthetic import StandInGAT, StandInTextEncoder, primekg_shaped_batch
@@ -732,8 +751,8 @@ def kernel_roofline(wl, prof, steps):
 
 
 def extra_workloads(args, dev):
-    """The default run (`bench.py`, cfg3 on one GPU) also times a few steps of the other workloads this build makes claims about, so
-    that those claims are measured by whoever runs the default command and not only by the builder: {name: {value, unit, ms_per_step,
+    """`bench.py --full` on the default workload (cfg3, one GPU) also times a few steps of the other workloads this build makes claims about,
+    so that those claims are measured by whoever runs that command and not only by the builder: {name: {value, unit, ms_per_step,
     dominant_kernel, bound, frac, clock_ghz, ...}}.  Each is a shortened `bench.py --workload <name>` (same classes, same timing
     protocol: warm-up, synchronise, K steps, synchronise); kernel durations of the multi-stream forwards come from a one-stream pass."""
     import medtok_amd.vector_quantization_soft_one_new as vqmod
@@ -818,14 +837,14 @@ def extra_workloads(args, dev):
         run("cfg4_vq_only", lambda: Cfg4(256, dev, 0, args.path, precomputed=True), 10, 4, clock=False)   # (the first steps grow the allocator's pools)
     finally:
         vqmod.TRAIN_SPLIT_TEXT_MAPPING = keep_map
-    out["note"] = ("short runs of `bench.py --workload <name>` inside the default command, after its timed region (same classes and timing protocol; "
+    out["note"] = ("short runs of `bench.py --workload <name>` inside `bench.py --full`, after its timed region (same classes and timing protocol; "
                    "`full*`: value from the multi-stream forward as shipped, kernel durations / frac from a one-stream pass; cfg4_vq_only = "
                    "--workload cfg4 --precomputed-encoders); rank-local")
     return out
 
 
 def collective_block(args, rank, world, dev):
-    """N > 1 only: the two partitionings of BASELINE config 5 that DO exchange data, so that the driver's unchanged command line
+    """N > 1 only: the two partitionings of BASELINE config 5 that DO exchange data, so that the driver's command line with --full
     (`bench.py --gpus N`, whose headline workload shards rows with no data-path collective) also measures RCCL over xGMI.
       cfg5_ema_step     600k rows in total row-sharded over the ranks, K = 16384: argmin + EMA statistics + ONE all-reduce of
                         [embed_sum | bins] (50.4 MB) + the fused codebook update -- strong scaling;
@@ -869,6 +888,52 @@ def collective_block(args, rank, world, dev):
     torch.cuda.empty_cache()
     out["backend"] = torch.distributed.get_backend()
     return out
+
+
+DUMP_BYTES = 60 * 2 ** 20          # data of all dumped arrays together (the .npy headers keep the files well under 64 MB)
+
+
+def dump_outputs(out, path, budget=DUMP_BYTES) -> None:
+    """Write `out` -- what a step returned: tensors and Python numbers, nested in dicts / tuples (names joined with '.') -- as
+    path/<name>.npy.  Floating tensors are written as float32 (float64 stays float64), integer / bool tensors and Python numbers as
+    float64 (exact for token ids); None entries are skipped.  When the arrays together exceed `budget`, every array of more than m
+    rows keeps only m of them, with m as large as fits: the sorted sample of a fixed seed, the same for every array of the same row
+    count (so rows correspond across outputs) and in every run."""
+    import numpy as np
+    flat = {}
+
+    def walk(name, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{name}.{k}" if name else str(k), x)
+        elif isinstance(v, (tuple, list)):
+            for i, x in enumerate(v):
+                walk(f"{name}.{i}", x)
+        elif isinstance(v, torch.Tensor):
+            flat[name] = v.detach()
+        elif isinstance(v, (bool, int, float)):
+            flat[name] = torch.tensor(float(v), dtype=torch.float64)
+    walk("", out)
+    dtype = {k: torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64 for k, t in flat.items()}
+    rows = {k: t.shape[0] if t.dim() else 1 for k, t in flat.items()}
+    row_bytes = {k: (t.numel() // max(rows[k], 1)) * (4 if dtype[k] == torch.float32 else 8) for k, t in flat.items()}
+
+    def size(m):
+        return sum(min(rows[k], m) * row_bytes[k] for k in flat)
+    m = max(rows.values(), default=0)
+    if size(m) > budget:
+        lo, hi = 1, m                    # largest m with size(m) <= budget
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if size(mid) <= budget else (lo, mid - 1)
+        m = lo
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, t in flat.items():
+        if rows[k] > m:
+            idx = np.sort(np.random.default_rng(0).choice(rows[k], m, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(d / f"{k}.npy", t.to(dtype[k]).cpu().numpy())
 
 
 def spawn_ranks(args) -> int:
@@ -958,21 +1023,27 @@ def main():
     if not events_behind:
         ops.profile_begin()              # library brackets each search-kernel launch with HIP events on its stream
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         wl.step()
+    last = wl.step()                     # (what the timed path returned in its last step: --dump-outputs)
     torch.cuda.synchronize(dev)
     mdist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = mdist.max_over_ranks(time.perf_counter() - t0, dev)
+    prof = None if events_behind else ops.profile_end()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(dict(zip(wl.OUTPUTS, last)) if isinstance(last, tuple) else last, args.dump_outputs)
+    del last
+    # Everything below the headline runs with --full only (a plain run ends with the line)
     events_pass_ms = None
-    if events_behind:
+    if events_behind and args.full:
         ops.profile_begin()
         t1 = time.perf_counter()
         for _ in range(args.steps):
             wl.step()
         torch.cuda.synchronize(dev)
         events_pass_ms = (time.perf_counter() - t1) / max(args.steps, 1) * 1e3
-    prof = ops.profile_end()
+        prof = ops.profile_end()
     # The shader clock the steps run at (the chip clocks to its power budget, and boxes differ by a few per cent -- as much as a round's
     # kernel work moves the headline): one idle wavefront per XCD on a stream of its own counts shader cycles against the 100 MHz
     # counter over `clock_steps` FURTHER steps right behind the timed region (same state of the chip; the timed region itself runs
@@ -982,7 +1053,7 @@ def main():
     clock = None
     step_s = elapsed / max(args.steps, 1)
     single_stream = (args.workload not in ("full", "fullref", "cfg4") or (args.one_stream and args.workload != "cfg4")) and step_s >= 0.005
-    if single_stream and not args.no_clock_probe:
+    if args.full and single_stream and not args.no_clock_probe:
         clock_steps = max(2, min(args.steps, int(0.5 / max(step_s, 1e-4))))
         with ops.ClockProbe(dev, max_seconds=3.0 * step_s * clock_steps + 5.0) as probe:
             for _ in range(clock_steps):
@@ -993,7 +1064,7 @@ def main():
     # what the shortlist left behind, read once AFTER the timed region from one further step (device-side reduction of the candidate
     # counts; the count of rows handed to the exact kernel is the library's own device counter `fb_count`)
     fallback = None
-    if args.workload in ("cfg3", "refdefault") and args.path in (ops.PATH_AUTO, ops.PATH_F16_FILTER):
+    if args.full and args.workload in ("cfg3", "refdefault") and args.path in (ops.PATH_AUTO, ops.PATH_F16_FILTER):
         try:
             ops.FILTER_STATS = []
             wl.step()
@@ -1005,11 +1076,11 @@ def main():
         finally:
             ops.FILTER_STATS = None
     prof_note = None
-    if events_behind:
+    if events_behind and args.full:
         prof_note = (f"the same {args.steps} steps repeated right behind the timed region with the library's event pairs on ({events_pass_ms:.2f} ms per "
                      f"step there): a training step is ~180 library launches, the pairs around its dense products alone cost ~0.27 ms per step")
     one_stream_elapsed = None
-    if args.workload in ("full", "fullref") and not args.no_one_stream_pass and not args.one_stream:
+    if args.full and args.workload in ("full", "fullref") and not args.no_one_stream_pass and not args.one_stream:
         # The forward enqueues on several HIP streams: an event pair around a launch then also covers the other streams' kernels that
         # share the device with it (a 0.05 ms text-side product is "1.3 ms" beside the graph side's attention).  Kernel durations for
         # the roofline object come from a second pass of the same steps on ONE stream; `value` is the multi-stream timed region above.
@@ -1041,7 +1112,7 @@ def main():
     # full workload, extra: the same forward with the text features in fp16 -- what a caller under fp16 autocast hands over (the
     # reference's default mode, train_MedTok.py:212,394): no image pass, half the key bytes, two matrix passes per product
     half_text = None
-    if args.workload == "full" and not args.no_half_text_pass:
+    if args.full and args.workload == "full" and not args.no_half_text_pass:
         text32 = wl.text
         try:
             wl.text = text32.half()
@@ -1059,7 +1130,7 @@ def main():
 
     # the exact fp32-MFMA path on the same workload (1 step): the filter path returns the same bits, faster
     exact = None
-    if args.path == ops.PATH_AUTO and args.exact_steps > 0 and args.workload != "cfg4":
+    if args.full and args.path == ops.PATH_AUTO and args.exact_steps > 0 and args.workload != "cfg4":
         agree = wl.paths_agree()             # same state, same inputs, both paths: every output tensor must be bit-identical
         wl.set_path(ops.PATH_F32_MFMA)
         wl.step()
@@ -1079,15 +1150,19 @@ def main():
                               "avg_launch_ms": e_prof["ms"] / max(e_prof["launches"], 1)}}
         wl.set_path(args.path)
 
-    kname, kp, bound_view, f16x3, hbm_bound, prof = kernel_roofline(wl, prof, args.steps)
-    achieved = bound_view.get("mfma_view", bound_view).get("achieved")
-    traffic, traffic_source = pmc_traffic(wl.name, kname, rows)
-    alg_bytes_step = float(wl.bytes_per_code()) * rows                # SURVEY 8d per-code figure x the codes one step processes (per GPU)
-    hbm_gbs = alg_bytes_step * args.steps / elapsed / 1e9
+    # (the dominant kernel also names `dtype`; a plain cfg4 run records no events, and its `dtype` is its own)
+    kname, f16x3 = None, False
+    if prof is not None:
+        kname, kp, bound_view, f16x3, hbm_bound, prof = kernel_roofline(wl, prof, args.steps)
+    if args.full:
+        achieved = bound_view.get("mfma_view", bound_view).get("achieved")
+        traffic, traffic_source = pmc_traffic(wl.name, kname, rows)
+        alg_bytes_step = float(wl.bytes_per_code()) * rows                # SURVEY 8d per-code figure x the codes one step processes (per GPU)
+        hbm_gbs = alg_bytes_step * args.steps / elapsed / 1e9
 
     # N > 1 under the headline workload: also time the two partitionings that exchange data (RCCL all-reduce / all-gather)
     strong = None
-    if world > 1 and args.workload == "cfg3" and not args.no_collectives:
+    if args.full and world > 1 and args.workload == "cfg3" and not args.no_collectives:
         del wl.h, wl.pooled_text, wl.pooled_graph
         torch.cuda.empty_cache()
         try:
@@ -1121,6 +1196,7 @@ def main():
                        "parallelism": (f"code-shard x{world}: all-gather of the per-rank k-lists (n*k*12 B per rank) + exact merge"
                                        if args.workload == "codeshard" else
                                        f"row-shard x{world}, codebook replicated, no data-path collective")},
+            **({
             "roofline": {**bound_view,
                          "traffic": traffic, "traffic_source": traffic_source,
                          # fabric bytes of the WHOLE step (every kernel) over its SURVEY-8d algorithmic bytes: re-reads through the L2s /
@@ -1149,8 +1225,9 @@ def main():
             # shader clock of further steps of the same workload right behind the timed region (ops.ClockProbe): separates the box (its power
             # budget / silicon) from the code when two lines differ by a few per cent; the dense-MFMA peaks above are quoted at 2.4 GHz
             "clock": clock,
+            } if args.full else {}),
         }
-        ir = issue_roofs(wl.name, kname, rows, kp["ms"] / max(kp["launches"], 1), (clock or {}).get("ghz_mean"))
+        ir = issue_roofs(wl.name, kname, rows, kp["ms"] / max(kp["launches"], 1), (clock or {}).get("ghz_mean")) if args.full else None
         if ir is not None:
             line["roofline"]["issue_roofs"] = ir
         if strong is not None:
@@ -1162,12 +1239,12 @@ def main():
             line["config"]["streams"] = "one (--one-stream)" if args.one_stream else "main + side streams (modality-specific searches, text side; the image pass over fp32 text rows has its own only where the attention kernel does not split the keys itself)"
             if half_text is not None:
                 line["half_precision_text"] = half_text
-            if args.workload == "full" and not args.no_one_stream_pass:
+            if args.full and args.workload == "full" and not args.no_one_stream_pass:
                 try:
                     line["no_host_read"] = wl.no_host_read(max(args.steps, 5))
                 except Exception as exc:           # (an extra: the headline line is printed regardless)
                     line["no_host_read"] = {"error": f"{type(exc).__name__}: {exc}"[:400]}
-            if args.workload == "fullref" and hasattr(wl, "graph_replay"):
+            if args.full and args.workload == "fullref" and hasattr(wl, "graph_replay"):
                 try:
                     line["hip_graph_replay"] = wl.graph_replay(max(args.steps, 20))
                 except Exception as exc:           # (an extra: the headline line is printed regardless)
@@ -1177,8 +1254,9 @@ def main():
                                       "ms_per_step": one_stream_elapsed / args.steps * 1e3,
                                       "note": "the same steps with every launch on ONE HIP stream (per-kernel event timing on; rank-local)"}
         if args.workload == "cfg4":
-            enc = wl.encoder_ms()
             line["dtype"] = "bf16 autocast (encoders, projections); the searches, their backward and the losses run in f32"
+        if args.full and args.workload == "cfg4":
+            enc = wl.encoder_ms()
             line["config"]["encoders_ms_per_step"] = enc
             line["config"]["vq_path_ms_per_step"] = max(line["ms_per_step"] - enc, 0.0)
             line["config"]["note"] = ("stand-in encoders (out of scope, upstream of the path); vq_path = cross-attention + 6 searches + "
@@ -1201,15 +1279,15 @@ def main():
                 line["with_max_nodes_bound"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
             finally:
                 wl.model.quantize.cross_attn.max_nodes_bound = None
-        if world == 1 and args.workload == "cfg3" and args.data == "gaussian" and args.rows is None and not args.no_extra_workloads:
+        if args.full and world == 1 and args.workload == "cfg3" and args.data == "gaussian" and args.rows is None and not args.no_extra_workloads:
             del wl.h, wl.pooled_text, wl.pooled_graph
             torch.cuda.empty_cache()
             line.setdefault("extra", {})["workloads"] = extra_workloads(args, dev)
         cpu_rows = args.cpu_rows if args.cpu_rows is not None else {"full": 512, "fullref": 512, "cfg4": 256}.get(args.workload, 16384)
-        if world == 1 and cpu_rows > 0:
+        if args.full and world == 1 and cpu_rows > 0:
             line["cpu_baseline"] = wl.cpu_baseline(cpu_rows)
             line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
-        else:
+        elif args.full:
             line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
     mdist.barrier()

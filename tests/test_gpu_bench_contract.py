@@ -1,4 +1,4 @@
-"""GPU: bench.py prints ONE JSON line that carries the driver's contract fields plus `roofline` and `cpu_baseline`
+"""GPU: bench.py prints ONE JSON line that carries the driver's contract fields; with --full also `roofline` and `cpu_baseline`
 (reduced row counts so the test takes seconds; the numbers themselves are not checked here)."""
 import json
 import subprocess
@@ -18,7 +18,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
                                   ["--workload", "full", "--rows", "256", "--cpu-rows", "8"],
                                   ["--workload", "cfg4", "--rows", "32", "--text-layers", "1", "--cpu-rows", "16"]])
 def test_bench_prints_one_contract_line(dev, args):
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", *args],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--full", *args],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -41,12 +41,40 @@ def test_bench_prints_one_contract_line(dev, args):
         assert r["events_pass_ms_per_step"] > 0 and "repeated right behind the timed region" in r["timed_in"]
 
 
+def test_plain_bench_line_is_the_headline_and_dumps_the_same_outputs(dev, tmp_path):
+    """Without --full the line is the headline alone (no extra pass behind the timed region), --steps sets the timed steps, and
+    --dump-outputs writes what the last timed step returned -- a seeded row sample within 64 MB, the same files in two runs."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--rows", "20000",
+                              "--dump-outputs", str(tmp_path / f"run{i}")], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert REQUIRED - {"roofline", "cpu_baseline"} <= set(d)
+    assert not {"roofline", "cpu_baseline", "exact_fp32_path", "clock", "fallback_rows", "extra"} & set(d)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"].startswith("f32 results")
+    assert abs(d["value"] - 20000 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    files = sorted(p.name for p in (tmp_path / "run0").iterdir())
+    assert files == ["embedding.npy", "tokens.npy", "weights.npy"] and files == sorted(p.name for p in (tmp_path / "run1").iterdir())
+    assert sum((tmp_path / "run0" / f).stat().st_size for f in files) <= 64e6
+    a = {f: np.load(tmp_path / "run0" / f) for f in files}
+    rows = a["embedding.npy"].shape[0]
+    assert 1000 < rows < 20000 and a["embedding.npy"].shape == (rows, 4 * 768) and a["tokens.npy"].shape == (rows, 4, 5)
+    assert a["embedding.npy"].dtype == np.float32 and a["tokens.npy"].dtype == np.float64 and a["weights.npy"].dtype == np.float32
+    for f in files:
+        assert np.array_equal(a[f], np.load(tmp_path / "run1" / f)), f
+
+
 def test_default_bench_line_carries_the_secondary_workloads(dev):
-    """`python bench.py` as the driver runs it (cfg 3 at full size, one GPU): besides the contract fields the line carries
-    extra.workloads -- short runs of the other workloads, so that the secondary claims are measured by whoever runs the default
-    command -- the per-search traffic unit, the step's fabric / algorithmic ratio and the device-side fallback and candidate statistics.
+    """`python bench.py --full` (cfg 3 at full size, one GPU): besides the contract fields the line carries
+    extra.workloads -- short runs of the other workloads, so that the secondary claims are measured by whoever runs the benchmark
+    -- the per-search traffic unit, the step's fabric / algorithmic ratio and the device-side fallback and candidate statistics.
     No entry may have failed."""
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-rows", "0"],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--cpu-rows", "0"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -71,7 +99,7 @@ def test_bench_data_distributions_off_the_gaussian(dev):
     rows the shortlist handed to the exact kernel and how many candidates it kept per row"""
     for data in ("near_codes", "clustered_codebook", "heavy_tail"):
         out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "1", "--warmup", "1", "--rows", "20000", "--cpu-rows", "0",
-                              "--exact-steps", "1", "--data", data], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                              "--exact-steps", "1", "--full", "--data", data], capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
         assert data in d["config"]["workload"]
@@ -99,7 +127,7 @@ def test_two_rank_bench_on_one_gpu(dev, workload):
     env = dict(os.environ, MEDTOK_DIST_BACKEND="gloo")
     out = run_with_retry(lambda port: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                        "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                                       "--workload", workload, "--rows", "20000"], cwd=ROOT, env=env)
+                                       "--workload", workload, "--rows", "20000", "--full"], cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -116,15 +144,15 @@ def test_bench_gpus_2_starts_its_own_ranks(dev):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     from conftest import run_with_retry
-    out = run_with_retry(lambda port: [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "20000"],
-                         cwd=ROOT, env=env)              # (bench.py picks its own port; the argument is unused here)
+    out = run_with_retry(lambda port: [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "20000",
+                                                     "--full"], cwd=ROOT, env=env)              # (bench.py picks its own port; the argument is unused here)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["n_ranks_seen"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["rows_per_gpu"] == 20000
-    # the unchanged driver command also times the two partitionings that exchange data (cfg 5): collective timings are in the line
+    # with --full the driver command also times the two partitionings that exchange data (cfg 5): collective timings are in the line
     ss = d["extra"]["strong_scaling"]
     e, c = ss["cfg5_ema_step"], ss["codeshard_search"]
     assert e["collective"] == "all_reduce" and e["collectives_per_step"] == 1 and e["collective_bytes_per_step"] == 16384 * 769 * 4

@@ -239,6 +239,38 @@ def test_bench_recorded_counter_figures_carry_their_provenance():
     assert bench.issue_roofs("refdefault", "filter_f16_kernel", 600000, 1.35, None) is None       # no clock probe: no figure
 
 
+def test_bench_dump_outputs_names_dtypes_and_seeded_row_sample(tmp_path):
+    """bench.py --dump-outputs: nested step results become <name>.npy in float32 / float64; over the byte budget every array keeps the
+    same seeded rows (rows correspond across outputs of one row count), the sample is the same in every call, and it fits the budget."""
+    import importlib.util
+    from pathlib import Path
+    import numpy as np
+    import torch
+    root = Path(__file__).resolve().parents[1]
+    spec = importlib.util.spec_from_file_location("bench_mod3", root / "bench.py")
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    n = 1000
+    out = {"emb": torch.arange(n * 8, dtype=torch.float32).reshape(n, 8), "ids": torch.arange(n * 2, dtype=torch.int64).reshape(n, 2),
+           "loss": (torch.tensor(1.5, dtype=torch.float16), torch.tensor([2.0, 3.0], dtype=torch.float64)), "usage": 0.25,
+           "aug": None, "small": torch.ones(10, 3, dtype=torch.bfloat16)}
+    bench.dump_outputs(out, tmp_path / "all")
+    got = {p.name: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(got) == {"emb.npy", "ids.npy", "loss.0.npy", "loss.1.npy", "usage.npy", "small.npy"}
+    assert got["emb.npy"].dtype == np.float32 and np.array_equal(got["emb.npy"], out["emb"].numpy())
+    assert got["ids.npy"].dtype == np.float64 and np.array_equal(got["ids.npy"], out["ids"].numpy())
+    assert got["loss.0.npy"].dtype == np.float32 and got["loss.0.npy"].shape == () and got["loss.1.npy"].dtype == np.float64
+    assert got["usage.npy"].dtype == np.float64 and float(got["usage.npy"]) == 0.25 and got["small.npy"].dtype == np.float32
+    budget = 100 * (8 * 4 + 2 * 8) + 10 * 3 * 4 + 16 + 10 + 8          # room for 100 rows of the two large arrays
+    for d in ("a", "b"):
+        bench.dump_outputs(out, tmp_path / d, budget=budget)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sum(v.nbytes for v in a.values()) <= budget and a["emb.npy"].shape == (100, 8) and a["small.npy"].shape == (10, 3)
+    rows = a["emb.npy"][:, 0] / 8                                     # row r of emb starts with 8 r; of ids with 2 r
+    assert np.array_equal(rows, a["ids.npy"][:, 0] / 2) and np.all(np.diff(rows) > 0) and rows.min() >= 0 and rows.max() < n
+    for f in a:
+        assert np.array_equal(a[f], np.load(tmp_path / "b" / f)), f
+
+
 def test_unsupported_k_fails_at_construction():
     """k beyond the kernels' list length (or beyond a region's size) is refused when the module is built, not at the first search."""
     from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer

@@ -3,16 +3,16 @@
 # usage: bash tools/profile_round5.sh   (writes under gpurun_out/r05/)
 export TMPDIR=/tmp
 out=gpurun_out/r05; mkdir -p $out
-python3 bench.py 2>/dev/null | tail -1 > $out/bench_cfg3.json
-python3 bench.py --workload full 2>/dev/null | tail -1 > $out/bench_full.json
-python3 bench.py --workload fullref --steps 20 --warmup 3 2>/dev/null | tail -1 > $out/bench_fullref.json
-python3 bench.py --workload fullref --rows 4096 --steps 10 --warmup 2 2>/dev/null | tail -1 > $out/bench_fullref_rows4096.json
-python3 bench.py --workload refdefault 2>/dev/null | tail -1 > $out/bench_refdefault.json
-python3 bench.py --workload cfg2 2>/dev/null | tail -1 > $out/bench_cfg2.json
-python3 bench.py --workload cfg5 2>/dev/null | tail -1 > $out/bench_cfg5.json
-python3 bench.py --workload codeshard 2>/dev/null | tail -1 > $out/bench_codeshard.json
-python3 bench.py --workload cfg4 2>/dev/null | tail -1 > $out/bench_cfg4.json
-python3 bench.py --workload cfg4 --precomputed-encoders 2>/dev/null | tail -1 > $out/bench_cfg4_vq_only.json
+python3 bench.py --full 2>/dev/null | tail -1 > $out/bench_cfg3.json
+python3 bench.py --full --workload full 2>/dev/null | tail -1 > $out/bench_full.json
+python3 bench.py --full --workload fullref --steps 20 --warmup 3 2>/dev/null | tail -1 > $out/bench_fullref.json
+python3 bench.py --full --workload fullref --rows 4096 --steps 10 --warmup 2 2>/dev/null | tail -1 > $out/bench_fullref_rows4096.json
+python3 bench.py --full --workload refdefault 2>/dev/null | tail -1 > $out/bench_refdefault.json
+python3 bench.py --full --workload cfg2 2>/dev/null | tail -1 > $out/bench_cfg2.json
+python3 bench.py --full --workload cfg5 2>/dev/null | tail -1 > $out/bench_cfg5.json
+python3 bench.py --full --workload codeshard 2>/dev/null | tail -1 > $out/bench_codeshard.json
+python3 bench.py --full --workload cfg4 2>/dev/null | tail -1 > $out/bench_cfg4.json
+python3 bench.py --full --workload cfg4 --precomputed-encoders 2>/dev/null | tail -1 > $out/bench_cfg4_vq_only.json
 for w in cfg3 full fullref refdefault; do
   extra=""; [ $w = full ] || [ $w = fullref ] && extra="--one-stream --no-one-stream-pass --no-half-text-pass"
   steps=2; [ $w = fullref ] && steps=6

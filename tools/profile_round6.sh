@@ -3,21 +3,21 @@
 # usage: bash tools/profile_round6.sh   (writes under gpurun_out/r06p/)
 export TMPDIR=/tmp
 out=gpurun_out/r06p; mkdir -p $out
-( time python3 bench.py > $out/bench_cfg3.json 2> $out/bench_cfg3.err ) 2> $out/bench_cfg3.time
-python3 bench.py --workload full 2>/dev/null | tail -1 > $out/bench_full.json
-python3 bench.py --workload full --rows 256 --steps 20 --warmup 3 2>/dev/null | tail -1 > $out/bench_full_rows256.json
-python3 bench.py --workload fullref --steps 50 --warmup 5 2>/dev/null | tail -1 > $out/bench_fullref.json
-python3 bench.py --workload fullref --rows 4096 --steps 10 --warmup 2 2>/dev/null | tail -1 > $out/bench_fullref_rows4096.json
-python3 bench.py --workload refdefault 2>/dev/null | tail -1 > $out/bench_refdefault.json
-python3 bench.py --workload cfg2 2>/dev/null | tail -1 > $out/bench_cfg2.json
-python3 bench.py --workload cfg5 2>/dev/null | tail -1 > $out/bench_cfg5.json
-python3 bench.py --workload codeshard 2>/dev/null | tail -1 > $out/bench_codeshard.json
-python3 bench.py --workload cfg4 --precomputed-encoders --steps 20 --warmup 20 2>/dev/null | tail -1 > $out/bench_cfg4_vq_only.json
-python3 bench.py --workload cfg4 --steps 10 --warmup 3 2>/dev/null | tail -1 > $out/bench_cfg4.json
+( time python3 bench.py --full > $out/bench_cfg3.json 2> $out/bench_cfg3.err ) 2> $out/bench_cfg3.time
+python3 bench.py --full --workload full 2>/dev/null | tail -1 > $out/bench_full.json
+python3 bench.py --full --workload full --rows 256 --steps 20 --warmup 3 2>/dev/null | tail -1 > $out/bench_full_rows256.json
+python3 bench.py --full --workload fullref --steps 50 --warmup 5 2>/dev/null | tail -1 > $out/bench_fullref.json
+python3 bench.py --full --workload fullref --rows 4096 --steps 10 --warmup 2 2>/dev/null | tail -1 > $out/bench_fullref_rows4096.json
+python3 bench.py --full --workload refdefault 2>/dev/null | tail -1 > $out/bench_refdefault.json
+python3 bench.py --full --workload cfg2 2>/dev/null | tail -1 > $out/bench_cfg2.json
+python3 bench.py --full --workload cfg5 2>/dev/null | tail -1 > $out/bench_cfg5.json
+python3 bench.py --full --workload codeshard 2>/dev/null | tail -1 > $out/bench_codeshard.json
+python3 bench.py --full --workload cfg4 --precomputed-encoders --steps 20 --warmup 20 2>/dev/null | tail -1 > $out/bench_cfg4_vq_only.json
+python3 bench.py --full --workload cfg4 --steps 10 --warmup 3 2>/dev/null | tail -1 > $out/bench_cfg4.json
 for d in near_codes clustered_codebook heavy_tail; do
-  python3 bench.py --data $d --steps 3 --warmup 1 --cpu-rows 0 2>/dev/null | tail -1 > $out/bench_cfg3_data_$d.json
+  python3 bench.py --full --data $d --steps 3 --warmup 1 --cpu-rows 0 2>/dev/null | tail -1 > $out/bench_cfg3_data_$d.json
 done
-python3 bench.py --workload refdefault --data clustered_codebook --steps 3 --warmup 1 --cpu-rows 0 2>/dev/null | tail -1 > $out/bench_refdefault_data_clustered_codebook.json
+python3 bench.py --full --workload refdefault --data clustered_codebook --steps 3 --warmup 1 --cpu-rows 0 2>/dev/null | tail -1 > $out/bench_refdefault_data_clustered_codebook.json
 for w in cfg3 full fullref; do
   extra=""; [ $w = full ] || [ $w = fullref ] && extra="--one-stream --no-one-stream-pass --no-half-text-pass"
   steps=2; [ $w = fullref ] && steps=6
