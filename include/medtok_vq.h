@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MEDTOK_VQ_ABI_VERSION 2
+#define MEDTOK_VQ_ABI_VERSION 3
 /* codes per row a search returns: 1 .. 16.  Lists of up to 8 run on either search path; 9 .. 16 (the reference takes any k,
  * vector_quantization_soft_one_new.py:91) always take the exact fp32 path, as two passes of lists of 8 (the 8 best, then the best
  * among the codes behind the row's 8th (distance, index) pair) -- the same total order as one list of k. */
@@ -210,6 +210,31 @@ int medtok_soft_assign_f32(const float *xref, const float *what, const int64_t *
  * (the mean of the squared error: :169-173,208-209; F.mse_loss at
  * norm_ema_quantizer.py:212). */
 int medtok_sum_scale_f32(const float *vals, int64_t n, double scale, float *out, void *stream);
+
+/* ---- decode: (token ids, weights) -> embedding -------------------------------------------------
+ * The inverse of what a forward stores per code (inference.py:110,136-138: tokens_all.npy [N, 4, k], weights_all.npy [N, 4, k]):
+ * for row r and slot s,  out[r, s*d : (s+1)*d] = sum_j weights[r, s, j] * what[region_lo[s] + tokens[r, s, j]]  over the NORMALISED
+ * codebook what [n_codes, d] -- the code mix of vector_quantization_soft_one_new.py:164-165,205, per element one fp32 chain
+ * acc = +0; acc = fmaf(w_j, e_j, acc) for j = 0 .. topk-1 in list order (medtok_soft_assign_f32 with MEDTOK_ASSIGN_RAW: the same bits).
+ * tokens int64 [n, slots, topk] are REGION-LOCAL ids as the forwards return them; slot s reads the codes [region_lo[s], + region_size[s]).
+ * region_lo / region_size are HOST arrays of `slots` entries (1 <= slots <= 4); out has row stride out_stride floats (0 = slots * d), so
+ * a call can fill a column block of a wider tensor.  One launch for all slots; 1 <= topk <= MEDTOK_MAX_TOPK.
+ * Ids are validated on the device: an id outside [0, region_size[s]) is never used as an address -- that row's block of slot s is
+ * written as zeros and bit s of *status (a device int the caller zeroed; may be NULL) is set.  Nothing traps and nothing is read back:
+ * the caller decides when to look at the word. */
+int medtok_decode_tokens_f32(const int64_t *tokens, const float *weights, int64_t n, int slots, int topk,
+                             const float *what, int64_t n_codes, int d, const int64_t *region_lo, const int64_t *region_size,
+                             float *out, int64_t out_stride, int *status, void *stream);
+/* Backward of the above from g_out [n, slots * d] (row stride g_stride floats, 0 = slots * d):
+ *   g_w[r, s, j]                     = <g_out[r, s block], what[region_lo[s] + tokens[r, s, j]]>    (fixed-order reduction)
+ *   g_code[(r*slots + s)*topk + j,:] = weights[r, s, j] * g_out[r, s block]     the gradient w.r.t. the NORMALISED code
+ *   g_ids[(r*slots + s)*topk + j]    = region_lo[s] + tokens[r, s, j]           its row of the codebook (GLOBAL id)
+ * g_w alone, or g_code together with g_ids, may be NULL.  Sum g_code per id with medtok_ema_stats_f32 (row order, no float atomics),
+ * then medtok_normalize_backward_sparse_f32 takes the sums to codebook.weight.  A (row, slot) with a bad id contributes zeros (its
+ * g_ids entries name the region's first code) and sets bit s of *status as in the forward. */
+int medtok_decode_tokens_backward_f32(const float *g_out, int64_t g_stride, const int64_t *tokens, const float *weights, int64_t n,
+                                      int slots, int topk, const float *what, int64_t n_codes, int d, const int64_t *region_lo,
+                                      const int64_t *region_size, float *g_w, float *g_code, int64_t *g_ids, int *status, void *stream);
 
 /* ---- fp32-accurate dense products on the fp16 matrix pipe (the projections around the cross-attention core:
  * nn.MultiheadAttention's in_proj / out_proj and the folded W_k / W_v products, vector_quantization_soft_one_new.py:17-51).

@@ -21,7 +21,7 @@ def use_library(path) -> None:
     _SO = Path(path)
 _lib = None
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 MAX_TOPK = 16
 PATH_AUTO, PATH_F32_MFMA, PATH_F16_FILTER = 0, 1, 2
 
@@ -72,6 +72,8 @@ SIGNATURES = {
     "medtok_debug_filter_stats": (_int, [_vp, _sz, _int, _i64, _i64, _int, _int, _int, _vp, _vp]),
     "medtok_soft_assign_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _i64, _vp, _vp]),
     "medtok_sum_scale_f32": (_int, [_vp, _i64, _dbl, _vp, _vp]),
+    "medtok_decode_tokens_f32": (_int, [_vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "medtok_decode_tokens_backward_f32": (_int, [_vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "medtok_soft_vq_backward_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     "medtok_normalize_backward_f32": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp]),
     "medtok_normalize_backward_sparse_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _vp, _vp]),
@@ -165,6 +167,7 @@ class DkvSource(C.Structure):
 
 DKV_SOURCES_MAX = 4
 MULTI_SEARCH_MAX = 6
+DECODE_MAX_SLOTS = 4
 USAGE_MULTI_MAX = 6
 
 

@@ -1864,6 +1864,75 @@ extern "C" int medtok_sum_scale_f32(const float *vals, int64_t n, double scale, 
     return check_launch("sum_scale");
 }
 
+// ================================================================= decode: (token ids, weights) -> embedding, and its backward
+#include "decode_kernels.h"
+
+// the argument checks both decode entries share; fills the per-slot regions the kernels take by value
+static int decode_args(const char *fn, int64_t n, int slots, int topk, int64_t n_codes, int d, const int64_t *region_lo,
+                       const int64_t *region_size, DecodeRegions &reg)
+{
+    if (n < 0 || d <= 0 || (d & 3)) return fail("%s: bad shape n=%ld d=%d (need n >= 0, d > 0, d %% 4 == 0)", fn, (long)n, d);
+    if (slots < 1 || slots > MEDTOK_DECODE_MAX_SLOTS) return fail("%s: slots=%d unsupported (1 .. %d)", fn, slots, MEDTOK_DECODE_MAX_SLOTS);
+    if (topk < 1 || topk > MEDTOK_MAX_TOPK) return fail("%s: topk=%d unsupported", fn, topk);
+    if (n_codes < 1 || n_codes >= (1ll << 31)) return fail("%s: n_codes=%ld unsupported", fn, (long)n_codes);
+    if (!region_lo || !region_size) return fail("%s: region_lo and region_size are required", fn);
+    for (int s = 0; s < MEDTOK_DECODE_MAX_SLOTS; ++s) {
+        const int t = s < slots ? s : 0;
+        if (region_lo[t] < 0 || region_size[t] < 1 || region_lo[t] > n_codes - region_size[t])
+            return fail("%s: region %d = [%ld, +%ld) is not inside the %ld codes", fn, t, (long)region_lo[t], (long)region_size[t], (long)n_codes);
+        reg.lo[s] = (long)region_lo[t];
+        reg.size[s] = (long)region_size[t];
+    }
+    if (n > ((1ll << 31) - 1) * 4 / slots) return fail("%s: n=%ld rows x %d slots exceed one launch", fn, (long)n, slots);
+    return 0;
+}
+
+extern "C" int medtok_decode_tokens_f32(const int64_t *tokens, const float *weights, int64_t n, int slots, int topk, const float *what,
+                                        int64_t n_codes, int d, const int64_t *region_lo, const int64_t *region_size, float *out,
+                                        int64_t out_stride, int *status, void *stream)
+{
+    DecodeRegions reg;
+    if (int rc = decode_args("decode_tokens", n, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
+    if (out_stride == 0) out_stride = (int64_t)slots * d;
+    if (out_stride < (int64_t)slots * d || (out_stride & 3)) return fail("decode_tokens: out_stride must be >= slots * d and a multiple of 4");
+    if (n == 0) return 0;
+    if (!tokens || !weights || !what || !out) return fail("decode_tokens: tokens, weights, what and out are required");
+    const long items = (long)n * slots;
+    hipStream_t s = (hipStream_t)stream;
+    // (rows of at most 64 floats: sixteen lanes per (row, slot); lists of up to 8 codes keep the 8-slot instantiation, as soft_assign)
+#define MEDTOK_DECODE_LAUNCH(LANES, MAXK)                                                                                              \
+    hipLaunchKernelGGL((decode_tokens_kernel<LANES, MAXK>), dim3((unsigned)((items + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s, \
+                       tokens, weights, items, slots, topk, what, d, reg, out, (long)out_stride, status)
+    if (d <= 64) { if (topk <= 8) MEDTOK_DECODE_LAUNCH(16, 8); else MEDTOK_DECODE_LAUNCH(16, MEDTOK_MAX_TOPK); }
+    else         { if (topk <= 8) MEDTOK_DECODE_LAUNCH(64, 8); else MEDTOK_DECODE_LAUNCH(64, MEDTOK_MAX_TOPK); }
+#undef MEDTOK_DECODE_LAUNCH
+    return check_launch("decode_tokens");
+}
+
+extern "C" int medtok_decode_tokens_backward_f32(const float *g_out, int64_t g_stride, const int64_t *tokens, const float *weights, int64_t n,
+                                                 int slots, int topk, const float *what, int64_t n_codes, int d, const int64_t *region_lo,
+                                                 const int64_t *region_size, float *g_w, float *g_code, int64_t *g_ids, int *status,
+                                                 void *stream)
+{
+    DecodeRegions reg;
+    if (int rc = decode_args("decode_tokens_backward", n, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
+    if (g_stride == 0) g_stride = (int64_t)slots * d;
+    if (g_stride < (int64_t)slots * d || (g_stride & 3)) return fail("decode_tokens_backward: g_stride must be >= slots * d and a multiple of 4");
+    if (!g_w && !g_code) return fail("decode_tokens_backward: nothing to compute (g_w and g_code are both NULL)");
+    if ((g_code != nullptr) != (g_ids != nullptr)) return fail("decode_tokens_backward: g_code and g_ids go together");
+    if (n == 0) return 0;
+    if (!g_out || !tokens || !weights || !what) return fail("decode_tokens_backward: g_out, tokens, weights and what are required");
+    const long items = (long)n * slots;
+    hipStream_t s = (hipStream_t)stream;
+#define MEDTOK_DECODE_LAUNCH(LANES, MAXK)                                                                                                       \
+    hipLaunchKernelGGL((decode_tokens_backward_kernel<LANES, MAXK>), dim3((unsigned)((items + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s, \
+                       g_out, (long)g_stride, tokens, weights, items, slots, topk, what, d, reg, g_w, g_code, g_ids, status)
+    if (d <= 64) { if (topk <= 8) MEDTOK_DECODE_LAUNCH(16, 8); else MEDTOK_DECODE_LAUNCH(16, MEDTOK_MAX_TOPK); }
+    else         { if (topk <= 8) MEDTOK_DECODE_LAUNCH(64, 8); else MEDTOK_DECODE_LAUNCH(64, MEDTOK_MAX_TOPK); }
+#undef MEDTOK_DECODE_LAUNCH
+    return check_launch("decode_tokens_backward");
+}
+
 // ================================================================= training half: sparse backward, normalize backward, InfoNCE
 #include "train_kernels.h"
 

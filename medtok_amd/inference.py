@@ -63,16 +63,19 @@ def quantize_pooled(vq: VectorQuantizer, h: torch.Tensor, pooled_text: torch.Ten
     return embedding, tokens, weights
 
 
-def save_outputs(out_dir, embeddings: np.ndarray, tokens: np.ndarray, weights: np.ndarray) -> None:
+def save_outputs(out_dir, embeddings: Optional[np.ndarray], tokens: np.ndarray, weights: np.ndarray, save_embeddings: bool = True) -> None:
+    """save_embeddings=False writes the two small arrays only: the table is determined by them and the codebook
+    (VectorQuantizer.decode; MedTokLookup.from_dir(..., quantizer=...) serves embed() from them)."""
     out = Path(out_dir)
     out.mkdir(parents=True, exist_ok=True)
-    np.save(out / "embeddings_all.npy", embeddings.astype(np.float32, copy=False))
+    if save_embeddings:
+        np.save(out / "embeddings_all.npy", embeddings.astype(np.float32, copy=False))
     np.save(out / "tokens_all.npy", tokens.astype(np.int64, copy=False))
     np.save(out / "weights_all.npy", weights.astype(np.float32, copy=False))
 
 
 @torch.no_grad()
-def run_inference(model: MultimodalTokenizer, batches: Iterable, out_dir: Optional[str] = None, device=None):
+def run_inference(model: MultimodalTokenizer, batches: Iterable, out_dir: Optional[str] = None, device=None, save_embeddings: bool = True):
     """Loop of inference.py:105-115 over `batches` (objects with the fields MultimodalTokenizer.forward
     reads plus `code_indices`), then order by code index and optionally write the three arrays.
 
@@ -86,7 +89,9 @@ def run_inference(model: MultimodalTokenizer, batches: Iterable, out_dir: Option
     other ranks return None.  (The reference lets every rank write its own shard over the same three files; the evident intent
     is one table of all codes, which is what the downstream readers of embeddings_all.npy expect.)
     `model` must be the bare module, not a DistributedDataParallel wrapper: inference synchronises no gradients, and DDP's
-    per-forward buffer broadcast would hang when the ranks hold different numbers of batches."""
+    per-forward buffer broadcast would hang when the ranks hold different numbers of batches.
+
+    save_embeddings=False: `out_dir` receives tokens_all.npy and weights_all.npy only (the return value is unchanged)."""
     from . import distributed as mdist
     model.eval()
     embs, toks, wts, order = [], [], [], []
@@ -170,5 +175,5 @@ def run_inference(model: MultimodalTokenizer, batches: Iterable, out_dir: Option
     tokens = tok[perm].numpy()
     weights = wt[perm].numpy()
     if out_dir is not None:
-        save_outputs(out_dir, embeddings, tokens, weights)
+        save_outputs(out_dir, embeddings, tokens, weights, save_embeddings=save_embeddings)
     return embeddings, tokens, weights

@@ -258,6 +258,88 @@ def soft_assign(xref, what, idx, dist, hard: bool = False, want_w: bool = True, 
     return w, zq, se
 
 
+DECODE_MAX_SLOTS = _lib.DECODE_MAX_SLOTS
+
+
+def _decode_args(fn, tokens, weights, what, regions, g_out=None):
+    """shared checks of decode_tokens / decode_tokens_backward: shapes and regions raise ValueError before any library call; tensors
+    that are not on the device raise MedTokLibraryError (_dev).  Returns (tokens [n, s, k], weights, what, lo[], size[])."""
+    if not isinstance(tokens, torch.Tensor) or not isinstance(weights, torch.Tensor) or not isinstance(what, torch.Tensor):
+        raise ValueError(f"{fn}: tokens, weights and what must be tensors")
+    if tokens.dtype != torch.int64 or weights.dtype != torch.float32 or what.dtype != torch.float32:
+        raise ValueError(f"{fn}: expected int64 tokens and fp32 weights / codebook, got {tokens.dtype}, {weights.dtype}, {what.dtype}")
+    if tokens.dim() == 2:
+        tokens, weights = tokens.unsqueeze(1), weights.unsqueeze(1) if weights.dim() == 2 else weights
+    if tokens.dim() != 3 or weights.shape != tokens.shape:
+        raise ValueError(f"{fn}: tokens and weights must both be [n, slots, k] (or [n, k]); got {tuple(tokens.shape)} and {tuple(weights.shape)}")
+    n, s, k = tokens.shape
+    if not 1 <= s <= DECODE_MAX_SLOTS or not 1 <= k <= MAX_TOPK:
+        raise ValueError(f"{fn}: {s} slots of {k} ids per row unsupported (1 .. {DECODE_MAX_SLOTS} slots, 1 .. {MAX_TOPK} ids)")
+    if what.dim() != 2 or what.shape[1] % 4 or what.shape[0] < 1:
+        raise ValueError(f"{fn}: the normalised codebook must be [n_codes, d] with d % 4 == 0, got {tuple(what.shape)}")
+    regions = [(0, what.shape[0])] * s if regions is None else [(int(lo), int(size)) for lo, size in regions]
+    if len(regions) != s:
+        raise ValueError(f"{fn}: {len(regions)} regions for {s} slots")
+    for lo, size in regions:
+        if lo < 0 or size < 1 or lo + size > what.shape[0]:
+            raise ValueError(f"{fn}: region [{lo}, +{size}) is not inside the {what.shape[0]} codes")
+    if g_out is not None and (not isinstance(g_out, torch.Tensor) or g_out.dtype != torch.float32 or g_out.shape != (n, s * what.shape[1])):
+        raise ValueError(f"{fn}: g_out must be fp32 [{n}, {s * what.shape[1]}]")
+    tokens, weights, what = _dev(tokens, "tokens", torch.int64), _dev(weights, "weights"), _dev(what, "what")
+    import ctypes as C
+    arr = C.c_int64 * s
+    return tokens, weights, what, arr(*[r[0] for r in regions]), arr(*[r[1] for r in regions])
+
+
+def decode_tokens(tokens, weights, what, regions=None, out=None, status=None):
+    """Embedding from stored tokens: out[r, s*d:(s+1)*d] = sum_j weights[r, s, j] * what[lo_s + tokens[r, s, j]] -> [n, slots * d].
+
+    tokens int64 / weights fp32 [n, slots, k] (or [n, k]: one slot), region-local ids; what [n_codes, d]: the NORMALISED codebook;
+    regions: per slot (lo, size) in rows of `what` (default: the whole table for every slot).  `out` may be a column block of a wider
+    tensor.  status: an int32 device tensor of one ZEROED element, or None; bit s is set when slot s held an id outside its region
+    (those blocks are written as zeros) -- nothing is read back here."""
+    tokens, weights, what, los, sizes = _decode_args("decode_tokens", tokens, weights, what, regions)
+    n, s, k = tokens.shape
+    d = what.shape[1]
+    zq, stride = _zq_out(out, n, s * d, what)
+    if status is not None:
+        status = _dev(status, "status", torch.int32)
+    lib = _lib.load()
+    with _on(what.device):
+        _lib.check(lib.medtok_decode_tokens_f32(tokens.data_ptr(), weights.data_ptr(), n, s, k, what.data_ptr(), what.shape[0], d, los, sizes,
+                                                zq.data_ptr(), stride, _ptr(status), _stream(what)), "medtok_decode_tokens_f32")
+    return zq
+
+
+def decode_tokens_backward(g_out, tokens, weights, what, regions=None, want_g_w: bool = True, want_g_code: bool = True, status=None):
+    """Backward of decode_tokens from g_out [n, slots * d]: (g_w [n, slots, k] or None, g_code [n * slots * k, d] or None, g_ids
+    [n * slots * k] int64 or None).  g_code[i] = w_i * g_out block is the gradient w.r.t. the normalised code what[g_ids[i]] (GLOBAL
+    ids): `ema_stats(g_code, g_ids, n_codes)` sums it per code in row order, `normalize_backward(..., live=bins)` takes it to the weight."""
+    if not want_g_w and not want_g_code:
+        raise ValueError("decode_tokens_backward: nothing to compute")
+    if g_out is None:
+        raise ValueError("decode_tokens_backward: g_out is required")
+    tokens, weights, what, los, sizes = _decode_args("decode_tokens_backward", tokens, weights, what, regions, g_out=g_out)
+    n, s, k = tokens.shape
+    d = what.shape[1]
+    if not g_out.is_cuda:
+        _dev(g_out, "g_out")
+    if n and not (g_out.stride(1) == 1 and g_out.stride(0) >= s * d and g_out.stride(0) % 4 == 0 and g_out.data_ptr() % 16 == 0):
+        g_out = g_out.contiguous()
+    if status is not None:
+        status = _dev(status, "status", torch.int32)
+    dev = what.device
+    g_w = torch.empty((n, s, k), dtype=torch.float32, device=dev) if want_g_w else None
+    g_code = torch.empty((n * s * k, d), dtype=torch.float32, device=dev) if want_g_code else None
+    g_ids = torch.empty(n * s * k, dtype=torch.int64, device=dev) if want_g_code else None
+    lib = _lib.load()
+    with _on(dev):
+        _lib.check(lib.medtok_decode_tokens_backward_f32(g_out.data_ptr(), g_out.stride(0) if n else 0, tokens.data_ptr(), weights.data_ptr(), n, s, k,
+                                                         what.data_ptr(), what.shape[0], d, los, sizes, _ptr(g_w), _ptr(g_code), _ptr(g_ids),
+                                                         _ptr(status), _stream(what)), "medtok_decode_tokens_backward_f32")
+    return g_w, g_code, g_ids
+
+
 def soft_vq_backward(x, xhat, what, idx, w, g_zq=None, g_xhat=None, g_out=None, g_vq=None, g_commit=None,
                      vq_scale: float = 0.0, commit_scale: float = 0.0, want_gx: bool = True, want_g_code: bool = True):
     """Sparse backward of the soft top-k assignment: (gx [n, d], g_code [n*k, d]).

@@ -123,6 +123,11 @@ class MultimodalTokenizer(nn.Module):
                                r["shared_text_embedding"], r["shared_graph_embedding"]), dim=-1)
         return embedding, tokens, weights
 
+    def detokenize(self, tokens, weights, validate=True):
+        """Embedding [B, 4*e_dim] from assemble()'s (tokens [B, 4, k], weights [B, 4, k]): its inverse, one decode launch
+        (VectorQuantizer.decode) instead of encoders, cross-attention and four searches."""
+        return self.quantize.decode(tokens, weights, types=("text", "graph", "shared", "shared"), validate=validate)
+
     def _map_text(self, feats):
         """text_mapped (reference tokenizer.py:118,221-222).  Under autograd on an MI355X: the library's own dense product, forward and
         backward (vector_quantization_soft_one_new.split_linear), like the quantiser's projections."""
@@ -191,23 +196,50 @@ class MedTokLookup:
     [num_codes, 4*e_dim] fp32, tokens_all.npy [num_codes, 4, k] int64, weights_all.npy
     [num_codes, 4, k] fp32, with rows in the order of `codes` (dataset_creator.py:255,273
     orders them by the med_code table).
+
+    `embeddings` may be None when a `quantizer` (a VectorQuantizer on an MI355X) is given instead: the table -- 7.4 GB at 600k
+    codes x 3072 floats against 144 MB of ids and weights -- is then never built; ids and weights are kept on the quantiser's device
+    and embed() decodes the requested rows on demand (VectorQuantizer.decode).  See from_tokens().
     """
 
-    def __init__(self, codes: Sequence[str], embeddings: np.ndarray, tokens: np.ndarray, weights: np.ndarray,
-                 region_offsets: Sequence[int] = (0, 0, 0, 0)):
-        if not (len(codes) == embeddings.shape[0] == tokens.shape[0] == weights.shape[0]):
+    def __init__(self, codes: Sequence[str], embeddings: Optional[np.ndarray], tokens: np.ndarray, weights: np.ndarray,
+                 region_offsets: Sequence[int] = (0, 0, 0, 0), quantizer: Optional[VectorQuantizer] = None):
+        if embeddings is None and quantizer is None:
+            raise ValueError("MedTokLookup: without embeddings a quantizer is needed to decode them from tokens and weights")
+        counts = [len(codes), tokens.shape[0], weights.shape[0]] + ([] if embeddings is None else [embeddings.shape[0]])
+        if len(set(counts)) != 1:
             raise ValueError("codes / embeddings / tokens / weights disagree on the number of codes")
         self.codes = list(codes)
         self.row = {c: i for i, c in enumerate(self.codes)}
         self.embeddings, self.tokens, self.weights = embeddings, tokens, weights
         self.region_offsets = np.asarray(region_offsets, dtype=np.int64).reshape(1, 4, 1)
+        self.quantizer = quantizer
+        self._dev_tokens = self._dev_weights = None
+        if embeddings is None:
+            if tokens.ndim != 3 or tokens.shape[1] != 4 or tokens.shape != weights.shape:
+                raise ValueError(f"MedTokLookup: tokens and weights must both be [num_codes, 4, k], got {tokens.shape} and {weights.shape}")
+            dev = quantizer.codebook.weight.device
+            self._dev_tokens = torch.from_numpy(np.ascontiguousarray(tokens, dtype=np.int64)).to(dev)
+            self._dev_weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float32)).to(dev)
 
     @classmethod
-    def from_dir(cls, path, codes: Sequence[str], region_offsets=(0, 0, 0, 0)):
+    def from_tokens(cls, codes: Sequence[str], tokens: np.ndarray, weights: np.ndarray, quantizer: VectorQuantizer,
+                    region_offsets=(0, 0, 0, 0)):
+        """A lookup without the embedding table: embed() decodes from (tokens, weights) and `quantizer`'s codebook on its device."""
+        return cls(codes, None, tokens, weights, region_offsets, quantizer=quantizer)
+
+    @classmethod
+    def from_dir(cls, path, codes: Sequence[str], region_offsets=(0, 0, 0, 0), quantizer: Optional[VectorQuantizer] = None):
+        """The arrays run_inference wrote.  embeddings_all.npy is used where it exists; where it does not (save_embeddings=False)
+        `quantizer` decodes the rows on demand."""
         from pathlib import Path
         p = Path(path)
-        return cls(codes, np.load(p / "embeddings_all.npy"), np.load(p / "tokens_all.npy"),
-                   np.load(p / "weights_all.npy"), region_offsets)
+        emb = p / "embeddings_all.npy"
+        if not emb.exists():
+            if quantizer is None:
+                raise FileNotFoundError(f"{emb} is absent: pass quantizer= to decode embeddings from tokens_all.npy / weights_all.npy")
+            return cls(codes, None, np.load(p / "tokens_all.npy"), np.load(p / "weights_all.npy"), region_offsets, quantizer=quantizer)
+        return cls(codes, np.load(emb), np.load(p / "tokens_all.npy"), np.load(p / "weights_all.npy"), region_offsets)
 
     def _rows(self, code):
         single = isinstance(code, str)
@@ -234,7 +266,12 @@ class MedTokLookup:
     def embed(self, code):
         """Quantised embedding [4*e_dim]."""
         rows, single = self._rows(code)
-        out = self.embeddings[rows]
+        if self.embeddings is None:
+            with torch.no_grad():
+                sel = torch.from_numpy(rows).to(self._dev_tokens.device)
+                out = self.quantizer.decode(self._dev_tokens[sel], self._dev_weights[sel]).cpu().numpy()
+        else:
+            out = self.embeddings[rows]
         return out[0] if single else out
 
     def __len__(self):

@@ -1522,6 +1522,37 @@ class _SoftVQFunction(torch.autograd.Function):
         return gx, gw, None, None, None, None, None
 
 
+class _DecodeFunction(torch.autograd.Function):
+    """VectorQuantizer.decode under autograd: embedding [N, S * d] from stored (tokens, weights) and the codebook weight.
+
+    Forward is the decode kernel (medtok_decode_tokens_f32).  Backward is ONE kernel (medtok_decode_tokens_backward_f32) for the
+    gradient of the weights and the per-(row, slot, j) gradients of the normalised codes; those are summed per code in row order
+    by the EMA-statistics kernels and taken through F.normalize exactly as _SoftVQFunction's code gradient is (no float atomics:
+    two runs give the same bits).  Nothing flows to the token ids."""
+
+    @staticmethod
+    def forward(ctx, weights, weight, tokens, what, regions, status):
+        out = ops.decode_tokens(tokens, weights.detach(), what, regions, status=status)
+        ctx.save_for_backward(weights, weight, tokens, what)
+        ctx.regions = regions
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        weights, weight, tokens, what = ctx.saved_tensors
+        want_w, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_w or want_c):
+            return None, None, None, None, None, None
+        g_w, g_code, g_ids = ops.decode_tokens_backward(g.float(), tokens, weights.detach(), what, ctx.regions, want_g_w=want_w, want_g_code=want_c)
+        gw = None
+        if want_c:
+            bins, g_what = ops.ema_stats(g_code, g_ids, what.shape[0])
+            gw = ops.normalize_backward(g_what, what, weight.detach(), live=bins)
+        if g_w is not None:
+            g_w = g_w.view(weights.shape)
+        return g_w, gw, None, None, None, None
+
+
 def _lib_multi_max():
     from . import _lib
     return _lib.MULTI_SEARCH_MAX
@@ -2130,6 +2161,78 @@ class VectorQuantizer(nn.Module):
         """Map region-local ids (what the searches return) to rows of codebook.weight."""
         lo, _ = self._region(types)
         return local_ids + lo
+
+    DECODE_TYPES = ("text", "graph", "shared")
+
+    def decode(self, tokens, weights, types=("text", "graph", "shared", "shared"), out=None, validate=True, global_ids=False):
+        """Embedding from stored tokens: the inverse of a forward's (ids, weights) -> [N, len(types) * e_dim].
+
+        tokens int64 / weights fp32 [N, S, k] -- as `MultimodalTokenizer.assemble` / tokens_all.npy / weights_all.npy hold them, slot s
+        searched over the region types[s] ("text", "graph" or "shared") -- or [N, k] with `types` a single string.  Ids are
+        region-local, as every forward returns them; global_ids=True takes rows of codebook.weight (what global_token_ids() gives).
+        Block s of a row is sum_j w_j * normalize(codebook.weight)[lo_s + id_j]: the eval-mode embedding of the forward that made the
+        tokens (its straight-through line changes the last bits only), in ONE launch for all slots.
+
+        Ids are checked on the device.  validate=True reads one status word back and raises ValueError naming the first slot that
+        held an id outside its region; validate=False reads nothing back (rows with a bad id come out as zeros), so the call can be
+        recorded into a HIP graph.  `out`: an fp32 [N, S * e_dim] device view to fill (e.g. a column block of a wider tensor); such a
+        call is not differentiable.  Otherwise, where autograd is recording and `weights` or `codebook.weight` requires a gradient,
+        both get one (the codebook's through F.normalize); the ids get none."""
+        single = isinstance(types, str)
+        kinds = (types,) if single else tuple(types)
+        if not 1 <= len(kinds) <= ops.DECODE_MAX_SLOTS or any(t not in self.DECODE_TYPES for t in kinds):
+            raise ValueError(f"decode: types must name 1 .. {ops.DECODE_MAX_SLOTS} of {self.DECODE_TYPES}, got {types!r}")
+        if not isinstance(tokens, torch.Tensor) or not isinstance(weights, torch.Tensor):
+            raise ValueError("decode: tokens and weights must be tensors")
+        if tokens.dtype != torch.int64 or weights.dtype != torch.float32:
+            raise ValueError(f"decode: expected int64 tokens and fp32 weights, got {tokens.dtype} and {weights.dtype}")
+        if single and tokens.dim() == 2 and weights.dim() == 2:
+            tokens, weights = tokens.unsqueeze(1), weights.unsqueeze(1)
+        if tokens.dim() != 3 or tokens.shape != weights.shape or tokens.shape[1] != len(kinds):
+            raise ValueError(f"decode: tokens and weights must both be [N, {len(kinds)}, k] for types={types!r}; got {tuple(tokens.shape)} "
+                             f"and {tuple(weights.shape)}")
+        n, s, k = tokens.shape
+        if not 1 <= k <= ops.MAX_TOPK:
+            raise ValueError(f"decode: k={k} ids per slot unsupported (1 .. {ops.MAX_TOPK})")
+        e, pad = self.e_dim, getattr(self, "_pad", 0)
+        if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == (n, s * e)):
+            raise ValueError(f"decode: out must be an fp32 [{n}, {s * e}] tensor")
+        for name, t in (("tokens", tokens), ("weights", weights)):
+            if not t.is_cuda:
+                raise ops._lib.MedTokLibraryError(f"decode: {name} is on {t.device}; expected a tensor on an MI355X (cuda/HIP) device -- "
+                                                  "medtok_amd has no CPU path")
+        regions = []
+        for t in kinds:
+            lo, hi = self._region(t)
+            regions.append((lo, hi - lo))
+        if global_ids:      # (one subtraction per slot with a host constant: no table of offsets to upload, so a graph can record it)
+            tokens = torch.stack([tokens[:, i] - regions[i][0] for i in range(s)], dim=1)
+        what = self._normalised_codebook()[0]
+        status = torch.zeros(1, dtype=torch.int32, device=tokens.device) if validate else None
+        wt = self.codebook.weight
+        if out is None and torch.is_grad_enabled() and (weights.requires_grad or wt.requires_grad):
+            wp = torch.nn.functional.pad(wt.float(), (0, pad)) if pad else wt.float()
+            res = _DecodeFunction.apply(weights, wp, tokens, what, tuple(regions), status)
+            if pad:
+                res = res.view(n, s, e + pad)[:, :, :e].reshape(n, s * e)
+        elif pad:
+            res = ops.decode_tokens(tokens, weights.detach(), what, regions, status=status).view(n, s, e + pad)[:, :, :e]
+            if out is not None:
+                out.copy_(res.reshape(n, s * e))
+                res = out
+            else:
+                res = res.reshape(n, s * e)
+        else:
+            res = ops.decode_tokens(tokens, weights.detach(), what, regions, out=out, status=status)
+        if validate:
+            word = int(status.item())
+            if word:
+                bad = (word & -word).bit_length() - 1
+                lo, size = regions[bad]
+                span = f"[{lo}, {lo + size})" if global_ids else f"[0, {size})"
+                raise ValueError(f"decode: slot {bad} ({kinds[bad]!r}) holds a token id outside {span}; slots with bad ids: "
+                                 f"{[i for i in range(s) if word >> i & 1]}")
+        return res
 
 
 def compute_entropy_loss(affinity, loss_type="softmax", temperature=0.01):
