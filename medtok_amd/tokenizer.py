@@ -133,7 +133,7 @@ class MultimodalTokenizer(nn.Module):
         backward (vector_quantization_soft_one_new.split_linear), like the quantiser's projections."""
         from . import vector_quantization_soft_one_new as vqmod
         lin = self.text_mapped
-        if (vqmod.SPLIT_PRODUCTS and vqmod.TRAIN_SPLIT_PRODUCTS and vqmod.TRAIN_SPLIT_TEXT_MAPPING and torch.is_grad_enabled() and feats.is_cuda and lin.weight.requires_grad
+        if (vqmod.SPLIT_PRODUCTS and vqmod.TRAIN_SPLIT_TEXT_MAPPING and torch.is_grad_enabled() and feats.is_cuda and lin.weight.requires_grad
                 and lin.in_features % 4 == 0 and lin.out_features % 4 == 0):
             return vqmod.split_linear(feats.reshape(-1, feats.shape[-1]), lin.weight, lin.bias).view(*feats.shape[:-1], lin.out_features)
         return lin(feats)

@@ -16,12 +16,16 @@ or library-GEMM path on the inference side at any batch size)
     layers, both directions and the node mean in two launches, no host read.  Other widths (<= 768): per layer the four dense
     products on the split-fp16 GEMM (ops.split_gemm, three MFMA passes over (hi, lo) images: fp32-accurate), the ragged
     attention core (ops.shared_kv_attention_split / shared_kv_attention), residual + LayerNorm in one kernel -- one C call per
-    layer and side (ops.cross_attention_layer).  Training / autograd: the same packed rows through _SplitLinearFunction
-    (three-pass products for fp32 callers, ONE half-precision pass under torch.autocast: ops.half_gemm) and
-    _RaggedAttentionFunction (HIP forward with dropout + HIP dQ / dKV backward);
+    layer and side (ops.cross_attention_layer).  Training / autograd: the same packed rows through the autograd layer of
+    medtok_amd/autograd.py -- _SplitLinearFunction (three-pass products for fp32 callers, ONE half-precision pass under
+    torch.autocast: ops.half_gemm) and _RaggedAttentionFunction / _TwoSidedAttentionFunction (HIP forward with dropout + HIP dQ / dKV
+    backward);
   - proj_text / proj_graph: the same GEMM kernels (project(), project_both());
-  - backward of a search: autograd.Function around ONE sparse kernel that only touches the k selected codes per row (the
-    reference back-propagates through a dense N x K matrix); the code gradients are summed per code without atomics.
+  - backward of a search: autograd.Function (autograd.py) around ONE sparse kernel that only touches the k selected codes per row
+    (the reference back-propagates through a dense N x K matrix); the code gradients are summed per code without atomics.
+
+This file holds the modules (CrossAttention, VectorQuantizer) and the eleven switches their code reads, each with the test that runs
+both of its positions; the autograd functions and their three switches are in autograd.py.
 
 Deviations from the reference, all additive or bug-compatible by intent
 (SURVEY.md section 0):
@@ -38,92 +42,72 @@ import torch
 import torch.nn as nn
 
 from . import ops
+# The autograd layer lives in medtok_amd/autograd.py (torch + ops only); split_linear and fan_out_text stay importable from here
+# for the tokenizer and for callers that knew them here.  Its three switches -- KEY_GRADIENT_SINK, TRAIN_BATCHED_SEARCHES,
+# TRAIN_STACK_SEARCHES_OF_A_REGION -- are attributes of THAT module: a switch lives in the one module whose code reads it.
+from .autograd import (_DecodeFunction, _HeadBlockDiag, _RaggedAttentionFunction, _SegmentMeanFunction, _SoftVQFunction,
+                       _SoftVQMultiFunction, _TwoSidedAttentionFunction, fan_out_text, split_linear)
 
+# The module's switches.  A switch is here only because a test runs both of its positions (named with it) or bench.py turns it; a
+# path that nothing exercises in its other position has no switch.
+#
 # The cross-attention layers run on combined weight products (one GEMM per side instead of in_proj -> per-head fold and per-head
 # Wv -> out_proj) while the extra flops of that form, 4 R D^2 (heads - 2) per layer, stay below this: launch-bound sizes (eight
 # launches of ~8 us saved per layer against ~70 us of fp32 GEMM at the bound).  Negative: never.
+# Both positions: tests/test_gpu_modules.py::test_cross_attention_combined_weights_match_two_step_form
 COMBINE_MAX_EXTRA_FLOPS = 8e9
-LPT_ORDER = True
 # Inference: the layers' dense products (and proj_text / proj_graph) run on the library's split-fp16 MFMA GEMMs
-# (CrossAttention._folded_rows_split) from this many packed query rows up.  1: always -- no library GEMM on the inference path at any
-# batch size (at the reference's own B = 256 the split form and the launch-bound combined-weight / hipBLASLt forms further down time
-# the same: 0.78-0.80 ms per forward, tools/r04/ab_fullref.py).
+# (CrossAttention._folded_rows_split) at every batch size -- no library GEMM on the inference path (at the reference's own B = 256
+# the split form and the launch-bound combined-weight / hipBLASLt forms further down time the same: 0.78-0.80 ms per forward,
+# tools/r04/ab_fullref.py).  Training / autograd: the same products and their backward through split_linear instead of
+# nn.functional.linear / einsum (hipBLASLt).
+# Both positions: tests/test_gpu_modules.py::test_cross_attention_combined_weights_match_two_step_form,
+# tests/test_gpu_split_gemm.py::test_projection_of_the_specific_searches_matches_nn_linear
 SPLIT_PRODUCTS = True
-SPLIT_MIN_ROWS = 1
-SPLIT_ATTENTION = True       # the graph side's attention on ops.shared_kv_attention_split (keys from fp16 images, made once per forward)
-SPLIT_ATTENTION_MIN_ROWS = 1024      # ... from this many query rows up (below it the image pass is not worth its launch)
-# which form of the wide-batch attention core ops.shared_kv_attention_split runs (include/medtok_vq.h): 2 = two 32-row tiles of a
-# code per block, one phase apart on one copy of the keys (D = 256 / 512 / 768; the others fall back to 0 inside the library)
-ATTENTION_VARIANT = 2
 # fp32 text rows go to the graph side's attention core as they are and become their (hi, lo) images inside the kernel, chunk by
-# chunk (variant 2 at D = 256 / 512 / 768): no image pass over the whole text batch, no image buffers
+# chunk (D = 256 / 512 / 768): no image pass over the whole text batch, no image buffers
+# Both positions: tests/test_gpu_modules.py::test_keys_split_inside_the_attention_kernel_equal_the_image_pass
 KEYS_SPLIT_IN_KERNEL = True
-# training / autograd: the cross-attention's dense products (and their backward) on the library's own split-fp16 GEMMs instead
-# of nn.functional.linear / einsum (hipBLASLt)
-TRAIN_SPLIT_PRODUCTS = True
 # inference: a layer's seven launches (images, four dense products, attention core, residual + LayerNorm) through ONE call of the
 # C ABI (medtok_cross_attention_layer_f32: the same kernels and bits; six fewer host round trips per layer and side)
+# Both positions: tests/test_gpu_modules.py::test_fused_layer_call_equals_the_seven_separate_calls
 FUSED_LAYER_CALL = True
-# ... and the tokenizer's text mapping (tokenizer.py:118, a Linear over every token of the batch: 131 072 rows at B = 256, L = 512) too.
-# Off by default: under autocast the library's half-precision GEMM is ~3x cheaper than the fp32-accurate three-pass product, and
-# that layer is upstream of the quantiser (bench.py --precomputed-encoders turns it on for the all-own-kernels profile).
+# training: the tokenizer's text mapping (tokenizer.py:118, a Linear over every token of the batch: 131 072 rows at B = 256, L = 512)
+# through split_linear too.  Off by default: under autocast the library's half-precision GEMM is ~3x cheaper than the fp32-accurate
+# three-pass product, and that layer is upstream of the quantiser.
+# Set by bench.py (--precomputed-encoders: the all-own-kernels profile); on in
+# tests/test_gpu_train_step.py::test_tokenizer_training_forward_maps_only_the_cls_row_of_the_aug_text
 TRAIN_SPLIT_TEXT_MAPPING = False
-# ... under torch.autocast those products run as ONE half-precision pass with fp32 accumulation (ops.half_gemm: the precision class
-# autocast gives the reference's nn.Linear / nn.MultiheadAttention, train_MedTok.py:212,394) instead of the fp32-accurate three-pass
-# form (3x the matrix work, device-side |x|_max prescales, lo images); fp32 callers keep the three-pass form
-AUTOCAST_HALF_PRODUCTS = True
-# ... and the attention forward of the graph side (many query rows per code) on the inference kernel's three-pass fp16 products with
-# dropout and log-sum-exp added (attention_pp.h, TRAIN form) instead of the exact fp32 matrix pipe: 420 -> ~165 us per layer at cfg 4
-AUTOCAST_SPLIT_ATTENTION_FORWARD = True
-# training: the two directions of the cross-attention share every layer's weights, so their rows go through the layer's dense
-# products in one launch per product (CrossAttention._pooled_packed)
-MERGE_SIDES_IN_TRAINING = True
-# training: all searches of a forward under one autograd node, so that the codebook receives ONE dense gradient (_SoftVQMultiFunction)
-TRAIN_SINGLE_CODEBOOK_GRADIENT = True
-# ... and their forward as ONE batched call (three launches: ops.soft_vq_forward_multi with per-row squared errors) where every search
-# takes the exact path with at most 4096 rows.  Off: measured SLOWER at cfg 4 (six searches of 256 rows over 49 152 / 16 384 codes:
-# 10.5 -> 10.9 ms per step, tools/r05/ab_cfg4_switch.py TRAIN_BATCHED_SEARCHES) -- the batched kernel's split plan is made for the
-# few hundred codes of the reference's default codebook; it pays at e_dim = 64, n_e = 600 (fewer launches), not here
-TRAIN_BATCHED_SEARCHES = False
-# ... the searches that share a region (the two shared ones; text and its aug view; graph and its aug view) as ONE search on their rows stacked
-TRAIN_STACK_SEARCHES_OF_A_REGION = True
 # inference at the reference's own width (e_dim = 64, 4 heads): the whole cross-attention of a forward -- both layers, both
 # directions, node mean -- in two launches with no host read (ops.cross_attention_small); needs a SORTED batch vector (PyG's are;
 # the kernels flag anything else in CrossAttention.small_status, checked wherever the forward synchronises anyway)
+# Both positions: tests/test_gpu_small_width.py::test_forward_small_width_equals_the_layer_by_layer_forward
 SMALL_WIDTH_FUSED = True
 # inference: the two shared searches of a forward as ONE search over the interleaved rows [text_0, graph_0, text_1, ...] (one
 # codebook pass, twice the rows per launch; its [2 B, e] result IS the [B, 2 e] shared embedding)
+# Both positions: tests/test_gpu_small_width.py::test_forward_small_width_equals_the_layer_by_layer_forward
 MERGE_SHARED_SEARCHES = True
 # inference on small batches (every search of the forward on the exact fp32 path with at most 4096 rows: ops.multi_search_eligible):
 # the forward's three to five searches in ONE call of three launches (ops.soft_vq_forward_multi) and its three to five updates of
 # the usage window in one call of two (ops.usage_update_multi_)
+# Both positions: tests/test_gpu_small_width.py::test_small_batch_forward_equals_the_general_forward, ..._at_d768_...
 BATCHED_SMALL_SEARCHES = True
 # inference: what every fp16-shortlist search derives from its codebook region (fp16 image, accumulator start values, largest norm)
 # is made ONCE per weight version, for all three regions together with the normalisation (ops.prepare_codebook: two launches),
 # instead of three passes over its region in each of a forward's three to five searches
+# Both positions: tests/test_gpu_filter.py::test_forward_with_and_without_a_prepared_codebook
 PREPARED_CODEBOOK = True
-# training under autocast: the row-major and the transposed 16-bit image of a product's input / upstream gradient from ONE pass over it
-# (ops.half_image_pair) instead of two
-FUSE_IMAGE_PAIRS = True
-# ... and a Linear's bias gradient (the column sums of its upstream gradient) from that same pass -- per 64-row tile in the kernel, over the
-# tiles in one small reduction -- instead of a reduction of its own over the gradient (104 us at 131 072 x 768)
-BIAS_GRADIENT_FROM_IMAGE_PASS = True
-# training: the text rows are read three ways -- as the keys of every cross-attention layer (:83,86: always the ORIGINAL text), as the
-# CLS query of the text side, as the CLS half of h (tokenizer.py:162) -- and autograd would sum their four [B L, D] gradients with a
-# zero fill and an add pass each (0.8 ms of a 12 ms step at B = 256, L = 512).  On: the layers' dKV kernels write into ONE buffer
-# (the first zeroes and stores, the others add), the CLS gradients are added to its B rows in place (_TextFanOut)
-KEY_GRADIENT_SINK = True
-# ... and the layers' dKV launches deferred to the node that collects the key gradient: ONE launch over all layers' queries writes the
-# [rows, D] matrix once (per-layer launches: a zero fill, a store and a read-add-store pass over it)
-DEFERRED_KEY_GRADIENT = True
 # training: both directions of a layer under ONE autograd node that writes their outputs (and dQ) into row ranges of one matrix, instead
 # of a split in front of two nodes and a concatenation behind them (a copy of the [R heads, D] matrix each, forward and backward)
+# Both positions: tests/test_gpu_train_step.py::test_two_sided_attention_node_equals_the_two_nodes
 TWO_SIDED_ATTENTION_NODE = True
-# CrossAttention.prepack(): pooled()'s prologue and the copy of its host-read values issued early by a caller that can (the tokenizer)
-PREPACK_CODES = True
-# training: the node mean of a code on the library's ordered segment mean under autograd (_SegmentMeanFunction) instead of a scatter into a
-# zero [B, max_nodes, D] tensor and a sum over it
-TRAIN_SEGMENT_MEAN = True
+
+# Tuning data and constants (not switches).
+SPLIT_ATTENTION_MIN_ROWS = 1024      # the graph side's attention on ops.shared_kv_attention_split (keys from fp16 images, made once per
+                                     # forward) from this many query rows up (below it the image pass is not worth its launch)
+# which form of the wide-batch attention core ops.shared_kv_attention_split runs (include/medtok_vq.h): two 32-row tiles of a code
+# per block, one phase apart on one copy of the keys (D = 256 / 512 / 768; the others fall back to form 0 inside the library)
+_SPLIT_CORE_VARIANT = 2
 from .norm_ema_quantizer import EmbeddingEMA
 
 USAGE_WINDOW = 300000   # vector_quantization_soft_one_new.py:118
@@ -135,10 +119,10 @@ UNSORTED_BATCH_MESSAGE = ("pooled(): the paths without a host read (assume_sorte
 # modality-specific searches and the text side's attention chain, about an eighth of a forward, all launches of a few hundred
 # blocks -- is enqueued on a second HIP stream and runs in the shadow of the graph side's chip-filling kernels; the streams join
 # before the shared searches.  From this many codes per call (below it a forward is launch-bound and a second stream only adds
-# host work); 0 turns it off.
+# host work); 0 turns it off.  The text side's launches are issued behind the graph side's first layer.
+# Both positions: tests/test_gpu_modules.py::test_side_stream_forward_equals_single_stream; set by bench.py (--one-stream, one_stream pass)
 SIDE_STREAM_MIN_CODES = 512
-STREAM_PRIORITY = (-1, 0, 0)       # text side (high), modality-specific searches, text images
-TEXT_CHAIN_AFTER_LAYER = 0         # the text side's launches are issued behind this graph-side layer (-1: in front of the graph side)
+STREAM_PRIORITY = (-1, 0, 0)       # text side (high), modality-specific searches, text images (tuning data, not a switch)
 _side_streams = {}
 
 
@@ -227,433 +211,6 @@ def _cached(holder, attr, key, build, device, rebuild=False):
         cur.wait_event(mark.event)
         _lend(cur, c[1])
     return c[1]
-
-
-class _SegmentMeanFunction(torch.autograd.Function):
-    """Mean of the attended nodes of every code (:140-141) under autograd: forward = the library's ordered segment mean (rows of a code
-    are adjacent), backward = each node row receives its code's gradient / node count (one division, one gather).  The training path
-    used to scatter the rows into a zero [B, max_nodes, D] tensor and sum it (157 MB at B = 256, max 200 nodes, D = 768)."""
-
-    @staticmethod
-    def forward(ctx, g, starts, counts, batch_sorted):
-        ctx.save_for_backward(counts, batch_sorted)
-        ctx.in_dtype = g.dtype
-        return ops.segment_mean(g.detach().float().contiguous(), starts, counts)
-
-    @staticmethod
-    def backward(ctx, d_out):
-        counts, batch_sorted = ctx.saved_tensors
-        per_code = d_out.float() / counts.clamp(min=1).unsqueeze(-1).to(torch.float32)
-        return per_code[batch_sorted].to(ctx.in_dtype), None, None, None
-
-
-class _KeyGradSink:
-    """Where the layers that share one key matrix leave its gradient during a backward (see _TextFanOut): either written by their dKV
-    kernels at once (`buf`: the first stores, the others add), or -- DEFERRED_KEY_GRADIENT -- as `pending` sources (a layer's queries,
-    upstream gradient, row statistics, mask parameters) that the collecting node turns into the gradient with ONE launch."""
-    __slots__ = ("buf", "node", "pending", "common")
-
-    def __init__(self):
-        self.buf = None         # the [rows, D] gradient while a backward is under way
-        self.node = None        # weak reference to the autograd node that collects it
-        self.pending = []       # sources of ops.shared_kv_attention_dkv_multi
-        self.common = None      # (kv, kv_start, kv_len, max_kv_len, half) of the pending sources
-
-
-def _sink_key_gradient(sink, q, q_start, q_len, kv, kv_start, kv_len, max_q_len, max_kv_len, scale, dropout_p, seed, out, lse, d_out, half, dq_into=None):
-    """dq of one attention call whose key gradient goes to `sink`: deferred as a source of the collecting node's one dKV launch where
-    the keys are those of the sources already there, else written / added by this call's own dKV kernel."""
-    common = (kv, kv_start, kv_len, max_kv_len, half)
-    same = sink.common is not None and all(a is b or (torch.is_tensor(a) and torch.is_tensor(b) and a.data_ptr() == b.data_ptr() and a.shape == b.shape)
-                                           or (not torch.is_tensor(a) and a == b) for a, b in zip(common, sink.common))
-    if DEFERRED_KEY_GRADIENT and sink.buf is None and len(sink.pending) < ops.DKV_SOURCES_MAX and (not sink.pending or same):
-        dq, delta = ops.shared_kv_attention_backward_dq(q, q_start, q_len, kv, kv_start, kv_len, max_q_len, max_kv_len, scale, dropout_p, seed, out, lse,
-                                                        d_out, half=half, dq_into=dq_into)
-        sink.pending.append(dict(q=q, d_out=d_out, lse=lse, delta=delta, q_start=q_start, q_len=q_len, scale=scale, dropout_p=dropout_p, seed=seed))
-        sink.common = common
-        return dq
-    first = sink.buf is None
-    if first:
-        sink.buf = torch.empty_like(kv)
-    dq, _ = ops.shared_kv_attention_backward(q, q_start, q_len, kv, kv_start, kv_len, max_q_len, max_kv_len, scale, dropout_p, seed, out, lse, d_out,
-                                             half=half, dkv_into=sink.buf, accumulate=not first, dq_into=dq_into)
-    return dq
-
-
-class _TextFan:
-    """carried by a text tensor that went through fan_out_text(): the CLS rows and the gradient sink of its keys"""
-    __slots__ = ("sink", "cls")
-
-    def __init__(self, sink, cls):
-        self.sink, self.cls = sink, cls
-
-
-class _TextFanOut(torch.autograd.Function):
-    """text [B, L, D] -> (the same rows, their CLS rows [B, D]) with ONE gradient buffer behind both: the attention layers whose keys
-    these rows are add their dKV into `sink` during the backward (and hand autograd no gradient for them), this node -- which the
-    engine runs after every consumer of its outputs -- adds the CLS gradient to the buffer's B first rows and passes it on."""
-
-    @staticmethod
-    def forward(ctx, text, sink):
-        ctx.sink = sink
-        ctx.seq_len = text.shape[1]
-        ctx.set_materialize_grads(False)
-        return text.view_as(text), text[:, 0].contiguous()
-
-    @staticmethod
-    def backward(ctx, g_rows, g_cls):
-        sink = ctx.sink
-        buf, sink.buf = sink.buf, None
-        pending, common, sink.pending, sink.common = sink.pending, sink.common, [], None
-        if pending:                         # the deferred key gradients of all layers: one launch, one store of the [rows, D] matrix
-            d = ops.shared_kv_attention_dkv_multi(pending, common[0], common[1], common[2], common[3], half=common[4])
-            buf = d if buf is None else buf.add_(d)
-        if g_rows is not None:              # (a consumer outside the sink protocol)
-            g_rows = g_rows.float()
-            buf = g_rows.clone() if buf is None else buf.view_as(g_rows).add_(g_rows)
-        if g_cls is not None:
-            if buf is None:
-                buf = g_cls.new_zeros((g_cls.shape[0], ctx.seq_len, g_cls.shape[1]), dtype=torch.float32)
-            buf = buf.view(g_cls.shape[0], -1, g_cls.shape[1])
-            buf[:, 0].add_(g_cls)
-        return (None if buf is None else buf.view(-1, ctx.seq_len, buf.shape[-1])), None
-
-
-def fan_out_text(text):
-    """The text rows [B, L, D] of a training step behind one gradient buffer (KEY_GRADIENT_SINK): returns the same values as a tensor
-    that carries `_medtok_fan` = (sink, CLS rows).  CrossAttention.pooled() and MultimodalTokenizer.quant() read the CLS rows from
-    there and route the key gradients of the attention layers into the sink; any other use of the returned tensor is ordinary
-    autograd.  Anything it does not apply to (no autograd, not an fp32 [B, L, D] tensor on an MI355X) is returned as it came."""
-    if getattr(text, "_medtok_fan", None) is not None:
-        return text
-    if not (KEY_GRADIENT_SINK and torch.is_tensor(text) and text.is_cuda and text.dim() == 3 and text.dtype == torch.float32
-            and text.requires_grad and torch.is_grad_enabled() and text.is_contiguous() and text.shape[1] > 0
-            and hasattr(torch._C, "_will_engine_execute_node")):
-        return text
-    import weakref
-    sink = _KeyGradSink()
-    rows, cls = _TextFanOut.apply(text, sink)
-    sink.node = weakref.ref(rows.grad_fn)
-    rows._medtok_fan = _TextFan(sink, cls)
-    return rows
-
-
-def _autocast_half():
-    """the half-precision dtype of the attention backward's products under torch.autocast (None: exact fp32 kernels)"""
-    if AUTOCAST_HALF_PRODUCTS and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") in (torch.float16, torch.bfloat16):
-        return torch.get_autocast_dtype("cuda")
-    return None
-
-
-def _split_forward(half, width, max_q_len, q_rows, kv_rows):
-    """the training forward on the three-pass fp16 kernel? (autocast callers, many query rows per code: see _RaggedAttentionFunction)"""
-    return (half is not None and AUTOCAST_SPLIT_ATTENTION_FORWARD and width in ops.ATTENTION_TRAIN_SPLIT_WIDTHS and max_q_len > 8
-            and q_rows > 0 and kv_rows > 0)
-
-
-def _live_sink(sink, needs_kv_grad):
-    """the sink if THIS backward will run the node that collects it (torch.autograd.grad() for other inputs does not), else None"""
-    if sink is None or not needs_kv_grad:
-        return None
-    node = sink.node() if sink.node is not None else None
-    return sink if (node is not None and torch._C._will_engine_execute_node(node)) else None
-
-
-class _TwoSidedAttentionFunction(torch.autograd.Function):
-    """Both directions of a training layer in ONE autograd node: query rows [0, cut) (the graph side: nodes x heads) attend to kv_a
-    (the text rows), rows [cut, n) (the text side: CLS x heads) to kv_b (the nodes) -- the two launches of _RaggedAttentionFunction
-    writing into row ranges of one output (and, backward, of one dQ) instead of a split in front and a concatenation behind, each a
-    copy of the [R heads, D] matrix forward and backward.  la / lb = (q_start, q_len, kv_start, kv_len, max_q_len, max_kv_len) per side."""
-
-    @staticmethod
-    def forward(ctx, qf, kv_a, kv_b, la, lb, cut, scale, dropout_p, seed_a, seed_b, sink):
-        q = qf.detach().float().contiguous()
-        ka, kb = kv_a.detach().float().contiguous(), kv_b.detach().float().contiguous()
-        ctx.half = _autocast_half()
-        n = q.shape[0]
-        out = torch.zeros_like(q)
-        lse = torch.full((n,), float("-inf"), dtype=torch.float32, device=q.device)
-        for lo, hi, kv, l, seed in ((0, cut, ka, la, seed_a), (cut, n, kb, lb, seed_b)):
-            if hi > lo:
-                ops.shared_kv_attention_train(q[lo:hi], l[0], l[1], kv, l[2], l[3], l[4], scale, dropout_p, seed,
-                                              split=_split_forward(ctx.half, q.shape[1], l[4], hi - lo, kv.shape[0]), out=out[lo:hi], lse=lse[lo:hi])
-        ctx.save_for_backward(q, ka, kb, out, lse, *la[:4], *lb[:4])
-        ctx.cfg = (cut, la[4], la[5], lb[4], lb[5], scale, dropout_p, seed_a, seed_b, qf.dtype, kv_a.dtype, kv_b.dtype)
-        ctx.sink = sink
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        q, ka, kb, out, lse, *lists = ctx.saved_tensors
-        cut, mq_a, mk_a, mq_b, mk_b, scale, dropout_p, seed_a, seed_b, qd, kad, kbd = ctx.cfg
-        n = q.shape[0]
-        d = d_out.float().contiguous()
-        dq = torch.empty_like(q)
-        dka = dkb = None
-        sink = _live_sink(ctx.sink, ctx.needs_input_grad[1])
-        if cut > 0:
-            a = lists[:4]
-            if sink is not None:
-                _sink_key_gradient(sink, q[:cut], a[0], a[1], ka, a[2], a[3], mq_a, mk_a, scale, dropout_p, seed_a, out[:cut], lse[:cut], d[:cut], ctx.half,
-                                   dq_into=dq[:cut])
-            else:
-                _, dka = ops.shared_kv_attention_backward(q[:cut], a[0], a[1], ka, a[2], a[3], mq_a, mk_a, scale, dropout_p, seed_a, out[:cut], lse[:cut],
-                                                          d[:cut], half=ctx.half, dq_into=dq[:cut])
-                dka = dka.to(kad)
-        elif ctx.needs_input_grad[1] and sink is None:
-            dka = torch.zeros_like(ka).to(kad)
-        if n > cut:
-            b = lists[4:]
-            _, dkb = ops.shared_kv_attention_backward(q[cut:], b[0], b[1], kb, b[2], b[3], mq_b, mk_b, scale, dropout_p, seed_b, out[cut:], lse[cut:], d[cut:],
-                                                      half=ctx.half, dq_into=dq[cut:])
-            dkb = dkb.to(kbd)
-        else:
-            dkb = torch.zeros_like(kb).to(kbd)
-        return dq.to(qd), dka, dkb, None, None, None, None, None, None, None, None
-
-
-class _RaggedAttentionFunction(torch.autograd.Function):
-    """The ragged attention core under autograd: forward = medtok_shared_kv_attention_train_f32 (dropout on the probabilities by
-    a stateless hash mask, log-sum-exp kept per row), backward = medtok_shared_kv_attention_backward_f32 (dQ and dKV kernels that
-    rebuild probabilities and mask; nothing of size rows x keys is stored).  fp32 whatever autocast says.
-    `sink` (a _KeyGradSink, or None): the key gradient goes into the sink's buffer instead of back to autograd."""
-
-    @staticmethod
-    def forward(ctx, q, kv, q_start, q_len, kv_start, kv_len, max_q_len, max_kv_len, scale, dropout_p, seed, sink=None):
-        qf, kvf = q.detach().float().contiguous(), kv.detach().float().contiguous()
-        # under torch.autocast the backward's four matrix products run as ONE half-precision pass (the reference's class there) and
-        # the forward on the three-pass fp16 products (fp32-accurate to ~1e-6: its log-sum-exp feeds the backward's softmax
-        # rebuild) where more than a few query rows share a code's keys; fp32 callers keep the exact fp32 kernels on both sides
-        ctx.half = _autocast_half()
-        split = _split_forward(ctx.half, qf.shape[1], max_q_len, qf.shape[0], kvf.shape[0])
-        out, lse = ops.shared_kv_attention_train(qf, q_start, q_len, kvf, kv_start, kv_len, max_q_len, scale, dropout_p, seed, split=split)
-        ctx.save_for_backward(qf, kvf, out, lse, q_start, q_len, kv_start, kv_len)
-        ctx.cfg = (max_q_len, max_kv_len, scale, dropout_p, seed, q.dtype, kv.dtype)
-        ctx.sink = sink
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        qf, kvf, out, lse, q_start, q_len, kv_start, kv_len = ctx.saved_tensors
-        max_q_len, max_kv_len, scale, dropout_p, seed, qd, kd = ctx.cfg
-        sink = _live_sink(ctx.sink, ctx.needs_input_grad[1])
-        if sink is not None:
-            dq = _sink_key_gradient(sink, qf, q_start, q_len, kvf, kv_start, kv_len, max_q_len, max_kv_len, scale, dropout_p, seed, out, lse,
-                                    d_out.float().contiguous(), ctx.half)
-            return dq.to(qd), None, None, None, None, None, None, None, None, None, None, None
-        dq, dkv = ops.shared_kv_attention_backward(qf, q_start, q_len, kvf, kv_start, kv_len, max_q_len, max_kv_len, scale, dropout_p, seed,
-                                                   out, lse, d_out.float().contiguous(), half=ctx.half)
-        return dq.to(qd), dkv.to(kd), None, None, None, None, None, None, None, None, None, None
-
-
-# split-K of the weight-gradient products (dW = dY^T X, contraction over the rows): at least this many rows per group.  A cfg 4 layer
-# has ~5 600 rows: at 2048 its [768, 768] gradients ran as 18 blocks of 256 x 256 on 256 CUs (56 us), its block-diagonal ones as 72 (146 us)
-SPLIT_K_MIN_ROWS = 512
-
-
-def _pad32(n):
-    return (int(n) + 31) // 32 * 32
-
-
-class _SplitLinearFunction(torch.autograd.Function):
-    """y = x W^T + b under autograd on the library's own dense product (medtok_split_gemm_scaled_f16: three fp16 MFMA passes over
-    (hi, lo) pairs, fp32-accurate) -- forward, data gradient dX = dY W and weight gradient dW = dY^T X are all "A . B^T" products of
-    split operands; the operands whose magnitude the host does not know (activations, upstream gradients) are prescaled by a power
-    of two taken from a device-side |.|_max, so nothing is read back.  fp32 in and out whatever autocast says (the reference's
-    projections, vector_quantization_soft_one_new.py:30,45, run in the autocast dtype: this is at least as accurate)."""
-
-    @staticmethod
-    def _weight_images(w, wf, npad_t):
-        """(amax, images [n, pad32(k)], transposed images [k, pad32(n)]) of a weight, per (storage, version): a parameter is used by
-        both attention directions of a step and by forward and backward -- one |w|_max and one split each instead of four.  Tensors
-        built inside the graph (the block-diagonal per-head weights) are new objects every forward and are simply split again."""
-        # (a slice of a parameter -- the q / k / v thirds of in_proj_weight -- is cached on the parameter it views)
-        holder = w if isinstance(w, nn.Parameter) else (w._base if isinstance(getattr(w, "_base", None), nn.Parameter) else None)
-        key = (w.data_ptr(), w._version, tuple(w.shape))
-        cache = getattr(holder, "_medtok_train_images", None) if holder is not None else None
-        if cache is not None and key[0] in cache and cache[key[0]][0] == key:
-            return cache[key[0]][1]
-        aw = ops.absmax(wf)
-        val = (aw, ops.split_half_scaled(wf, _pad32(wf.shape[1]), aw), ops.split_half_scaled(wf, npad_t, aw, transpose=True))
-        if holder is not None:
-            if cache is None:
-                cache = holder._medtok_train_images = {}
-            cache[key[0]] = (key, val)
-        return val
-
-    @staticmethod
-    def _half_images(w, dt, kp, npad):
-        """(w [n, pad32(k)], w^T [k, pad32(n)]) as dt (fp16 / bf16) matrices, per (storage, version, dtype) for parameters"""
-        holder = w if isinstance(w, nn.Parameter) else (w._base if isinstance(getattr(w, "_base", None), nn.Parameter) else None)
-        key = (w.data_ptr(), w._version, tuple(w.shape), dt)
-        cache = getattr(holder, "_medtok_half_images", None) if holder is not None else None
-        if cache is not None and (key[0], dt) in cache and cache[(key[0], dt)][0] == key:
-            return cache[(key[0], dt)][1]
-        w16 = w.detach().to(dt)
-        n, k = w16.shape
-        val = (torch.nn.functional.pad(w16, (0, kp - k)).contiguous() if kp != k else w16.contiguous(),
-               torch.nn.functional.pad(w16.t(), (0, npad - n)).contiguous())
-        if holder is not None:
-            if cache is None:
-                cache = holder._medtok_half_images = {}
-            cache[(key[0], dt)] = (key, val)
-        return val
-
-    @staticmethod
-    def _forward_half(ctx, x, w, b, dt):
-        """the autocast form: y = x16 w16^T + b, one half-precision pass with fp32 accumulation; the 16-bit operand images (and, in
-        the backward, their transposes) come from the library's own cast / transpose kernels"""
-        m, k = x.shape
-        n = w.shape[0]
-        kp, npad = _pad32(k), _pad32(n)
-        xf = x.detach().float()
-        xf = xf if xf.stride(1) == 1 and xf.stride(0) % 4 == 0 and xf.data_ptr() % 16 == 0 else xf.contiguous()
-        w16, wt16 = _SplitLinearFunction._half_images(w, dt, kp, npad)
-        # the weight gradient contracts over the rows: it reads x TRANSPOSED (split over the rows into `groups` chunks: see backward);
-        # that image comes out of the same pass over x as the forward's operand, and is what the backward keeps of x
-        groups, chunk, mp = _SplitLinearFunction._row_split(m, n, k)
-        if ctx.needs_input_grad[1]:
-            x16, xt16 = (ops.half_image_pair(xf, kp, mp, dt, group_cols=chunk) if FUSE_IMAGE_PAIRS else
-                         (ops.half_image(xf, kp, dt), ops.half_image(xf, mp, dt, transpose=True, group_cols=chunk)))
-        else:
-            x16, xt16 = ops.half_image(xf, kp, dt), None
-        y = ops.half_gemm(x16, w16, n_g=n, k_g=kp, bias=None if b is None else b.detach().float().contiguous())
-        ctx.save_for_backward(xt16, wt16)
-        ctx.shape = (m, k, n)
-        ctx.half = dt
-        ctx.dtypes = (x.dtype, w.dtype, None if b is None else b.dtype)
-        return y
-
-    @staticmethod
-    def _row_split(m, n, k):
-        """split-K of the weight-gradient product: (groups, rows per group (a multiple of 64), padded row count)"""
-        tiles = ((n + 255) // 256) * ((k + 255) // 256)
-        groups = max(1, min(256 // max(tiles, 1), m // SPLIT_K_MIN_ROWS))
-        chunk = (-(-m // groups) + 63) // 64 * 64
-        groups = -(-m // chunk)
-        return groups, chunk, groups * chunk
-
-    @staticmethod
-    def _backward_half(ctx, dy):
-        xt16, wt16 = ctx.saved_tensors
-        dxt, dwt, dbt = ctx.dtypes
-        m, k, n = ctx.shape
-        dt = ctx.half
-        npad = wt16.shape[1]
-        dyf = dy.detach().float().contiguous()
-        dx = dw = db = None
-        groups, chunk, mp = _SplitLinearFunction._row_split(m, n, k)
-        want_dx, want_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and xt16 is not None
-        want_db = dbt is not None and ctx.needs_input_grad[2]
-        if want_dx and want_dw and FUSE_IMAGE_PAIRS:              # both images of dY (and the bias gradient) from one pass over it
-            if want_db and BIAS_GRADIENT_FROM_IMAGE_PASS:
-                dy16, dyt16, db = ops.half_image_pair(dyf, npad, mp, dt, col_sums=True)
-                db = db.to(dbt)
-            else:
-                dy16, dyt16 = ops.half_image_pair(dyf, npad, mp, dt)
-        else:
-            dy16 = ops.half_image(dyf, npad, dt) if want_dx else None
-            if want_dw and want_db and BIAS_GRADIENT_FROM_IMAGE_PASS and m > 0:
-                dyt16, db = ops.half_image(dyf, mp, dt, transpose=True, col_sums=True)
-                db = db.to(dbt)
-            else:
-                dyt16 = ops.half_image(dyf, mp, dt, transpose=True) if want_dw else None
-        if want_dx:                          # dX [m, k] = dY [m, n] . (W^T [k, n])^T
-            dx = ops.half_gemm(dy16, wt16, n_g=k, k_g=npad).to(dxt)
-        if want_dw:                          # dW [n, k] = dY^T [n, m] . (X^T [k, m])^T, split over the rows in one grouped launch
-            dw = ops.half_gemm(dyt16, xt16, n_g=k, k_g=chunk, groups=groups, a_group_cols=chunk, b_group_rows=k)
-            dw = (dw.view(n, groups, k).sum(1) if groups > 1 else dw).to(dwt)
-        if want_db and db is None:
-            db = dyf.sum(0).to(dbt)
-        return dx, dw, db
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        m, k = x.shape
-        n = w.shape[0]
-        ctx.half = None
-        if (AUTOCAST_HALF_PRODUCTS and torch.is_autocast_enabled() and m > 0 and k % 8 == 0 and n % 4 == 0 and k % 4 == 0
-                and torch.get_autocast_dtype("cuda") in (torch.float16, torch.bfloat16)):
-            return _SplitLinearFunction._forward_half(ctx, x, w, b, torch.get_autocast_dtype("cuda"))
-        xf, wf = x.detach().float().contiguous(), w.detach().float().contiguous()
-        m, k = xf.shape
-        n = wf.shape[0]
-        kp = _pad32(k)
-        if m == 0:
-            ctx.shape = (0, k, n)
-            ctx.dtypes = (x.dtype, w.dtype, None if b is None else b.dtype)
-            return xf.new_zeros(0, n)
-        ax = ops.absmax(xf)
-        aw, w_img, wt_img = _SplitLinearFunction._weight_images(w, wf, _pad32(n))
-        y = ops.split_gemm_scaled(ops.split_half_scaled(xf, kp, ax), w_img, n_g=n, k_g=kp,
-                                  bias=None if b is None else b.detach().float().contiguous(), amax_a=ax, amax_b=aw)
-        ctx.save_for_backward(xf, ax, aw, *wt_img)
-        ctx.shape = (m, k, n)
-        ctx.dtypes = (x.dtype, w.dtype, None if b is None else b.dtype)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        if ctx.half is not None:
-            return _SplitLinearFunction._backward_half(ctx, dy)
-        dxt, dwt, dbt = ctx.dtypes
-        dyf = dy.float().contiguous()
-        m, k, n = ctx.shape
-        if m == 0:                           # no rows (a batch without graph nodes, an empty z): empty / zero gradients, like F.linear
-            return (dyf.new_zeros(0, k).to(dxt) if ctx.needs_input_grad[0] else None,
-                    dyf.new_zeros(n, k).to(dwt) if ctx.needs_input_grad[1] else None,
-                    dyf.new_zeros(n).to(dbt) if (dbt is not None and ctx.needs_input_grad[2]) else None)
-        xf, ax, aw, wt_hi, wt_lo = ctx.saved_tensors
-        ad = ops.absmax(dyf)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:          # dX [m, k] = dY [m, n] . (W^T [k, n])^T
-            npad = _pad32(n)
-            dx = ops.split_gemm_scaled(ops.split_half_scaled(dyf, npad, ad), (wt_hi, wt_lo), n_g=k, k_g=npad, amax_a=ad, amax_b=aw).to(dxt)
-        if ctx.needs_input_grad[1]:          # dW [n, k] = dY^T [n, m] . (X^T [k, m])^T: both operands transposed, contraction over the rows
-            # split-K in one grouped launch: the rows are cut into G chunks, group g multiplies chunk g of both operands into its own
-            # [n, k] block, the G blocks are summed (a [768, 768] gradient is nine 256 x 256 tiles: alone they would walk all the
-            # rows on nine CUs)
-            groups, chunk, mp = _SplitLinearFunction._row_split(m, n, k)
-            dw = ops.split_gemm_scaled(ops.split_half_scaled(dyf, mp, ad, transpose=True),
-                                       ops.split_half_scaled(xf, mp, ax, transpose=True, group_cols=chunk),
-                                       n_g=k, k_g=chunk, amax_a=ad, amax_b=ax, groups=groups, a_group_cols=chunk, b_group_rows=k)
-            dw = (dw.view(n, groups, k).sum(1) if groups > 1 else dw).to(dwt)
-        if dbt is not None and ctx.needs_input_grad[2]:
-            db = dyf.sum(0).to(dbt)
-        return dx, dw, db
-
-
-def split_linear(x, w, b=None):
-    return _SplitLinearFunction.apply(x, w, b)
-
-
-class _HeadBlockDiag(torch.autograd.Function):
-    """The block-diagonal matrix of a [H hd, D] projection weight's per-head blocks -- transposed: blocks w_h^T, [H D, H hd] (the fold
-    of W_k into the queries); else blocks w_h, [H hd, H D] (W_v on the per-head contexts) -- in two launches (zero fill + one
-    strided copy) with a one-launch backward (the diagonal blocks of the gradient, gathered).  torch.block_diag over H slices is
-    the same matrix in 5 launches forward and 11 backward (a zero [D, D] tensor, a copy and an add per slice)."""
-
-    @staticmethod
-    def forward(ctx, w, heads, transposed):
-        hd, dim = w.shape[0] // heads, w.shape[1]
-        ctx.cfg = (heads, hd, dim, transposed)
-        blocks = w.detach().view(heads, hd, dim)
-        if transposed:
-            out = w.new_zeros(heads * dim, heads * hd)
-            out.view(heads, dim, heads, hd).diagonal(dim1=0, dim2=2).copy_(blocks.permute(2, 1, 0))
-        else:
-            out = w.new_zeros(heads * hd, heads * dim)
-            out.view(heads, hd, heads, dim).diagonal(dim1=0, dim2=2).copy_(blocks.permute(1, 2, 0))
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        heads, hd, dim, transposed = ctx.cfg
-        if transposed:
-            gw = g.view(heads, dim, heads, hd).diagonal(dim1=0, dim2=2).permute(2, 1, 0)
-        else:
-            gw = g.view(heads, hd, heads, dim).diagonal(dim1=0, dim2=2).permute(2, 0, 1)
-        return gw.reshape(heads * hd, dim), None, None
 
 
 class CrossAttentionLayer(nn.Module):
@@ -874,7 +431,7 @@ class CrossAttention(nn.Module):
         if FUSED_LAYER_CALL and core_args is not None:
             a = core_args()
             r = ops.cross_attention_layer(rows, x, w, a["q_start"], a["q_len"], a["max_q_len"], a["kv"], a["kv_split"], a["kv_start"], a["kv_len"],
-                                          a["scale"], ATTENTION_VARIANT, ln.weight, ln.bias, ln.eps, want_images=next_split)
+                                          a["scale"], _SPLIT_CORE_VARIANT, ln.weight, ln.bias, ln.eps, want_images=next_split)
             if not next_split:
                 return r
             y, images = r
@@ -908,7 +465,7 @@ class CrossAttention(nn.Module):
         plain = not torch.is_grad_enabled() and not torch.is_autocast_enabled() and rows.dtype == wk.dtype
         ln = layer.layer_norm
         if (plain and not layer.training and rows.is_cuda and rows.dtype == torch.float32 and SPLIT_PRODUCTS and dim % 4 == 0
-                and ln.elementwise_affine and ln.bias is not None and mha.in_proj_bias is not None and n_rows >= SPLIT_MIN_ROWS
+                and ln.elementwise_affine and ln.bias is not None and mha.in_proj_bias is not None and n_rows > 0
                 and getattr(attend, "library_core", False)):
             return CrossAttention._folded_rows_split(layer, rows, attend, next_split)
         if plain and not layer.training and rows.is_cuda and 4.0 * n_rows * dim * dim * max(heads - 2, 0) <= COMBINE_MAX_EXTRA_FLOPS:
@@ -924,7 +481,7 @@ class CrossAttention(nn.Module):
             if dim % 4 == 0 and ln.elementwise_affine and ln.bias is not None:
                 return ops.residual_layernorm(rows, out, ln.weight, ln.bias, ln.eps)
             return ln(rows + out)
-        if (not plain and rows.is_cuda and SPLIT_PRODUCTS and TRAIN_SPLIT_PRODUCTS and dim % 4 == 0 and hd % 4 == 0
+        if (not plain and rows.is_cuda and SPLIT_PRODUCTS and dim % 4 == 0 and hd % 4 == 0
                 and mha.in_proj_bias is not None):
             # training / autograd: the four dense products and their backward on the library's own split-fp16 GEMMs
             # (_SplitLinearFunction).  The two per-head products become plain linears against BLOCK-DIAGONAL weights built with
@@ -999,10 +556,10 @@ class CrossAttention(nn.Module):
             if split_out:                                  # (inference on the library's core only: the kernel writes the (hi, lo) images itself)
                 assert qf.shape[1] == dim + pad and not autograd and core is ops.shared_kv_attention
                 if kv_split is not None:
-                    return ops.shared_kv_attention_split(q_in, q_start, q_len, kv_split, kv_start, kv_len, max_q_len, scale, split_out=True, variant=ATTENTION_VARIANT)
+                    return ops.shared_kv_attention_split(q_in, q_start, q_len, kv_split, kv_start, kv_len, max_q_len, scale, split_out=True, variant=_SPLIT_CORE_VARIANT)
                 return ops.shared_kv_attention(q_in, q_start, q_len, kv, kv_start, kv_len, max_q_len, scale, split_out=True)
             if kv_split is not None:                       # wide inference batches: 64-row blocks, keys by LDS-DMA from their fp16 images
-                out = ops.shared_kv_attention_split(q_in.float(), q_start, q_len, kv_split, kv_start, kv_len, max_q_len, scale, variant=ATTENTION_VARIANT)
+                out = ops.shared_kv_attention_split(q_in.float(), q_start, q_len, kv_split, kv_start, kv_len, max_q_len, scale, variant=_SPLIT_CORE_VARIANT)
             elif autograd:
                 p = float(mha.dropout) if self.training else 0.0
                 seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0.0 else 0      # host RNG: no device sync
@@ -1014,7 +571,7 @@ class CrossAttention(nn.Module):
             code = torch.arange(bsz, device=dev, dtype=torch.long)
             lists = dict(t_start=code * heads, t_len=torch.full((bsz,), heads, device=dev, dtype=torch.long),
                          g_start=starts * heads, g_len=counts * heads, tok_start=code * seq_len, g_kv_len=valid_len)
-            if LPT_ORDER and not autograd and bsz > 1:
+            if not autograd and bsz > 1:
                 order = torch.argsort(valid_len, descending=True)
                 for key in ("g_start", "g_len", "tok_start", "g_kv_len"):
                     lists[key] = lists[key][order]
@@ -1032,15 +589,14 @@ class CrossAttention(nn.Module):
         side = None
         text_split = images_ready = None
         # (wider than 768 -- BERT-large features -- only the image form runs, whatever the batch size)
-        want_images = (not autograd and core is ops.shared_kv_attention and text.is_cuda and kv_text.shape[1] in ops.ATTENTION_SPLIT_WIDTHS
-                       and SPLIT_ATTENTION and max_nodes > 0
+        want_images = (not autograd and core is ops.shared_kv_attention and text.is_cuda and kv_text.shape[1] in ops.ATTENTION_SPLIT_WIDTHS and max_nodes > 0
                        and (nodes_sorted.shape[0] * heads >= SPLIT_ATTENTION_MIN_ROWS or kv_text.shape[1] > ops.ATTENTION_MAX_TRAIN_WIDTH))
         def text_chain(cur):
             for i, layer in enumerate(self.model):
                 cur = self._folded_rows(layer, cur, text_attend, next_split=i + 1 < len(self.model))
             return cur
         use_side = lib_core and max_nodes > 0 and 0 < SIDE_STREAM_MIN_CODES <= bsz and not torch.is_grad_enabled()
-        if autograd and MERGE_SIDES_IN_TRAINING and max_nodes > 0 and nodes_sorted.dtype == cur.dtype:
+        if autograd and max_nodes > 0 and nodes_sorted.dtype == cur.dtype:
             # training: both directions share the layers' weights (:83,86), so the graph side's rows and the text side's CLS rows go
             # through every dense product of a layer TOGETHER -- one launch per product (and per gradient) instead of two, one
             # accumulation into each weight's .grad instead of two; only the attention core runs per side, on its row range
@@ -1064,7 +620,7 @@ class CrossAttention(nn.Module):
             for layer in self.model:
                 rows = self._folded_rows(layer, rows, both_attend)
             g, cur = torch.split(rows, [n_g, rows.shape[0] - n_g], dim=0)
-            if TRAIN_SEGMENT_MEAN and g.is_cuda and g.dtype == torch.float32 and dim % 4 == 0:
+            if g.is_cuda and g.dtype == torch.float32 and dim % 4 == 0:
                 gm = _SegmentMeanFunction.apply(g, starts, counts, batch_sorted)      # ordered sums per code (no atomics), one launch
                 return (cur, gm) if join else (cur, gm, None)
             if slot is None:
@@ -1080,9 +636,6 @@ class CrossAttention(nn.Module):
             side, main = _side_stream(text.device)
             # everything the text chain reads was born on the main stream and may be dropped by the host before the chain has run
             _lend(side, cur, text, kv_nodes, t_start, t_len, starts, counts)
-            if TEXT_CHAIN_AFTER_LAYER < 0:
-                with torch.cuda.stream(side):
-                    cur = text_chain(cur)
         else:
             cur = text_chain(cur)
         if max_nodes == 0:                                 # nothing to attend from: the node mean of every code is zero
@@ -1098,7 +651,7 @@ class CrossAttention(nn.Module):
                 return
             if images is not None:                         # (pooled() issued them before anything else)
                 text_split, images_ready = images
-            elif (KEYS_SPLIT_IN_KERNEL and ATTENTION_VARIANT == 2 and kv_text.dtype == torch.float32 and kv_text.is_contiguous()
+            elif (KEYS_SPLIT_IN_KERNEL and kv_text.dtype == torch.float32 and kv_text.is_contiguous()
                     and kv_text.shape[1] in ops.ATTENTION_HALF_KEY_WIDTHS):
                 text_split = kv_text                       # the fp32 rows themselves: the kernel splits every chunk it copies
             else:
@@ -1123,7 +676,7 @@ class CrossAttention(nn.Module):
                                                   kv_start=tok_start, kv_len=g_kv_len, scale=scale)
         for i, layer in enumerate(self.model):
             g = self._folded_rows(layer, g, graph_attend, next_split=i + 1 < len(self.model))
-            if use_side and i == min(TEXT_CHAIN_AFTER_LAYER, len(self.model) - 1):
+            if use_side and i == 0:
                 with torch.cuda.stream(side):
                     cur = text_chain(cur)
         pending = None
@@ -1135,7 +688,7 @@ class CrossAttention(nn.Module):
         if not autograd and not torch.is_grad_enabled() and g.is_cuda and g.dtype == torch.float32 and dim % 4 == 0:
             gm = ops.segment_mean(g, starts, counts)               # rows of a code are adjacent: one ordered chain per column
             return (cur, gm) if join else (cur, gm, pending)
-        if TRAIN_SEGMENT_MEAN and g.is_cuda and g.dtype == torch.float32 and dim % 4 == 0:
+        if g.is_cuda and g.dtype == torch.float32 and dim % 4 == 0:
             gm = _SegmentMeanFunction.apply(g, starts, counts, batch_sorted)          # (the same under autograd)
             return (cur, gm) if join else (cur, gm, pending)
         if slot is None:                                   # (pooled() leaves the in-code position of a node to this fallback)
@@ -1317,14 +870,14 @@ class CrossAttention(nn.Module):
         speed).  The next pooled() call on the same two tensors takes the result; any other call ignores it.  No-op off the GPU,
         with max_nodes_bound set (nothing is read then) or during a HIP-graph capture."""
         self._prepacked = None
-        if not (PREPACK_CODES and torch.is_tensor(text_mask) and torch.is_tensor(batch) and text_mask.is_cuda and batch.is_cuda and text_mask.dim() == 2
+        if not (torch.is_tensor(text_mask) and torch.is_tensor(batch) and text_mask.is_cuda and batch.is_cuda and text_mask.dim() == 2
                 and getattr(self, "max_nodes_bound", None) is None and not torch.cuda.is_current_stream_capturing()):
             return
         mha = self.model[0].multihead_attn
         if SMALL_WIDTH_FUSED and not self.training and not torch.is_grad_enabled() and mha.embed_dim == 64 and mha.num_heads == 4:
             return                          # (the two-launch small-width path has no prologue and no host read)
         b = batch.reshape(-1).to(torch.long)
-        lpt = LPT_ORDER and not (self.training or torch.is_grad_enabled())
+        lpt = not (self.training or torch.is_grad_enabled())
         pk = ops.pack_codes(text_mask, b, self.model[0].multihead_attn.num_heads, lpt)
         host = getattr(self, "_prepack_host", None)
         if host is None:
@@ -1379,7 +932,7 @@ class CrossAttention(nn.Module):
         # fp16 text features (a caller under fp16 autocast, the reference's default mode: train_MedTok.py:212,394) ARE the hi image of
         # the graph side's keys and have no lo part: no image pass, half the key bytes, two matrix passes per product instead of three
         half_keys = (not autograd and not torch.is_grad_enabled() and text.dtype == torch.float16 and text.is_contiguous()
-                     and SPLIT_ATTENTION and ATTENTION_VARIANT == 2 and dim in ops.ATTENTION_HALF_KEY_WIDTHS
+                     and dim in ops.ATTENTION_HALF_KEY_WIDTHS
                      and nodes.shape[0] * heads >= SPLIT_ATTENTION_MIN_ROWS)
         if half_keys:
             nodes = nodes.float()                          # (queries and the text side's keys: fp32)
@@ -1396,15 +949,15 @@ class CrossAttention(nn.Module):
             bound = int(bound)
             if bound <= 0:
                 raise ValueError(f"max_nodes_bound = {bound} must be a positive node count (or None)")
-            pk = ops.pack_codes(text_mask, batch, heads, LPT_ORDER and not autograd, count_bound=bound, status=self._status_word(text.device))
+            pk = ops.pack_codes(text_mask, batch, heads, not autograd, count_bound=bound, status=self._status_word(text.device))
         else:
-            early = self._take_prepacked(text_mask, batch, LPT_ORDER and not autograd)
-            pk = early[0] if early is not None else ops.pack_codes(text_mask, batch, heads, LPT_ORDER and not autograd)
+            early = self._take_prepacked(text_mask, batch, not autograd)
+            pk = early[0] if early is not None else ops.pack_codes(text_mask, batch, heads, not autograd)
         images = None
         if half_keys:
             images = ((text.view(bsz * seq_len, dim), None), None)
-        elif (not autograd and not torch.is_grad_enabled() and SPLIT_ATTENTION and 0 < SIDE_STREAM_MIN_CODES <= bsz
-                and not (KEYS_SPLIT_IN_KERNEL and ATTENTION_VARIANT == 2 and dim in ops.ATTENTION_HALF_KEY_WIDTHS)
+        elif (not autograd and not torch.is_grad_enabled() and 0 < SIDE_STREAM_MIN_CODES <= bsz
+                and not (KEYS_SPLIT_IN_KERNEL and dim in ops.ATTENTION_HALF_KEY_WIDTHS)
                 and text.dtype == torch.float32 and nodes.dtype == torch.float32 and text.is_contiguous()
                 and dim in ops.ATTENTION_SPLIT_WIDTHS and nodes.shape[0] * heads >= SPLIT_ATTENTION_MIN_ROWS and nodes.shape[0] > 0):
             # The (hi, lo) fp16 images of the valid text rows -- the keys of the graph side, an HBM-bound pass over the whole text
@@ -1481,159 +1034,6 @@ class CrossAttention(nn.Module):
             w = node_valid.transpose(0, 1).unsqueeze(-1).to(q_graph.dtype)
             pooled_graph = (q_graph * w).sum(0) / counts.clamp(min=1).unsqueeze(-1).to(q_graph.dtype)
         return pooled_text, pooled_graph
-
-
-class _SoftVQFunction(torch.autograd.Function):
-    """One search in train mode: (zq_ste, vq, commit, xhat, idx, w) from projected rows x and a codebook region.
-
-    Forward is the fused gfx950 path (rownorm -> search -> soft assign, medtok_soft_vq_forward_f32) plus the
-    fixed-order loss reduction.  Backward is ONE sparse kernel (medtok_soft_vq_backward_f32): per row only the k
-    selected codes carry gradient -- the dense N x K matrix the reference's autograd graph differentiates
-    (:120-125,157-182,203-214) is exactly zero everywhere else.  The per-(row, slot) code gradients are summed per
-    code in row order by the EMA-statistics kernels (no atomics: bit-reproducible), then taken through F.normalize.
-    The upstream gradients of vq / commit stay on the device (0-dim tensors); nothing synchronises the host."""
-
-    @staticmethod
-    def forward(ctx, x, weight, what, wsq, topk, path, beta):
-        ctx.set_materialize_grads(False)
-        r = ops.soft_vq_forward(x.detach(), what, wsq, topk, path, want_sqerr=True)
-        n, d = x.shape
-        vq = ops.sum_scale(r["row_sqerr"], (1.0 / (n * d)) if n else float("nan"))      # mean of nothing: nan, like F.mse_loss
-        commit = ops.sum_scale(r["row_sqerr"], beta / (n * d))
-        ctx.save_for_backward(x, weight, r["xhat"], what, r["idx"], r["w"])
-        ctx.beta = beta
-        ctx.mark_non_differentiable(r["idx"], r["w"])
-        return r["zq"], vq, commit, r["xhat"], r["idx"], r["w"]
-
-    @staticmethod
-    def backward(ctx, g_zq_ste, g_vq, g_commit, g_xhat, _gi, _gw):
-        x, weight, xhat, what, idx, w = ctx.saved_tensors
-        n, d = x.shape
-        want_x, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        as_f32 = lambda t: None if t is None else t.float()
-        gx, g_code = ops.soft_vq_backward(x.detach(), xhat, what, idx, w, g_xhat=as_f32(g_xhat), g_out=as_f32(g_zq_ste),
-                                          g_vq=as_f32(g_vq), g_commit=as_f32(g_commit),
-                                          vq_scale=2.0 / (n * d), commit_scale=2.0 * ctx.beta / (n * d),
-                                          want_gx=want_x, want_g_code=want_w)
-        gw = None
-        if want_w:
-            bins, g_what = ops.ema_stats(g_code, idx.reshape(-1), what.shape[0])
-            gw = ops.normalize_backward(g_what, what, weight.detach(), live=bins)
-        return gx, gw, None, None, None, None, None
-
-
-class _DecodeFunction(torch.autograd.Function):
-    """VectorQuantizer.decode under autograd: embedding [N, S * d] from stored (tokens, weights) and the codebook weight.
-
-    Forward is the decode kernel (medtok_decode_tokens_f32).  Backward is ONE kernel (medtok_decode_tokens_backward_f32) for the
-    gradient of the weights and the per-(row, slot, j) gradients of the normalised codes; those are summed per code in row order
-    by the EMA-statistics kernels and taken through F.normalize exactly as _SoftVQFunction's code gradient is (no float atomics:
-    two runs give the same bits).  Nothing flows to the token ids."""
-
-    @staticmethod
-    def forward(ctx, weights, weight, tokens, what, regions, status):
-        out = ops.decode_tokens(tokens, weights.detach(), what, regions, status=status)
-        ctx.save_for_backward(weights, weight, tokens, what)
-        ctx.regions = regions
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        weights, weight, tokens, what = ctx.saved_tensors
-        want_w, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (want_w or want_c):
-            return None, None, None, None, None, None
-        g_w, g_code, g_ids = ops.decode_tokens_backward(g.float(), tokens, weights.detach(), what, ctx.regions, want_g_w=want_w, want_g_code=want_c)
-        gw = None
-        if want_c:
-            bins, g_what = ops.ema_stats(g_code, g_ids, what.shape[0])
-            gw = ops.normalize_backward(g_what, what, weight.detach(), live=bins)
-        if g_w is not None:
-            g_w = g_w.view(weights.shape)
-        return g_w, gw, None, None, None, None
-
-
-def _lib_multi_max():
-    from . import _lib
-    return _lib.MULTI_SEARCH_MAX
-
-
-class _SoftVQMultiFunction(torch.autograd.Function):
-    """All searches of a training forward under ONE autograd node: (zq_ste, vq, commit, xhat, idx, w) per search from its rows and its
-    region of the codebook -- the per-search forward of _SoftVQFunction, search by search.  What changes is the BACKWARD of the codebook:
-    the per-(row, slot) code gradients of all searches are summed per code in ONE segmented sum over global code ids and taken through
-    F.normalize once, so the weight receives ONE dense gradient.  (Six _SoftVQFunction nodes on six slices of the weight hand autograd
-    six dense [n_e, D] gradients -- a zero fill and a copy each for the slices -- that it then adds up: 1.9 ms of fills and adds per
-    step at n_e = 49152, D = 768.)"""
-
-    @staticmethod
-    def forward(ctx, weight, what, wsq, topk, path, beta, regions, *xs):
-        ctx.set_materialize_grads(False)
-        outs, saved, nondiff = [], [], []
-        # a per-GPU batch of searches (at most 4096 rows each, the exact path): ONE call of three launches for all of them
-        # (ops.soft_vq_forward_multi: the per-search bits) instead of five launches per search
-        batched = None
-        if (TRAIN_BATCHED_SEARCHES and path in (ops.PATH_AUTO, ops.PATH_F32_MFMA) and 1 <= len(xs) <= _lib_multi_max() and topk <= 8
-                and all(x.is_cuda and x.shape[0] > 0 and ops.multi_search_eligible(x.shape[0], hi - lo, x.shape[1], topk) for x, (lo, hi) in zip(xs, regions))):
-            batched = ops.soft_vq_forward_multi([dict(x=x.detach().float(), what=what[lo:hi], wsq=wsq[lo:hi].contiguous()) for x, (lo, hi) in zip(xs, regions)],
-                                                topk, want_sqerr=True)
-        # the searches of ONE region (both shared ones; a modality's two views) as one call on their rows stacked: the region's codes are
-        # streamed once for both and five launches serve two searches (any row count gives every row the same bits: the library's plans
-        # only cut the code axis, and the per-split lists are joined in the (distance, index) total order)
-        stacked = {}
-        if batched is None and TRAIN_STACK_SEARCHES_OF_A_REGION and all(x.is_cuda and x.dim() == 2 for x in xs):
-            by_region = {}
-            for i, reg in enumerate(regions):
-                by_region.setdefault((tuple(reg), xs[i].shape[1], xs[i].dtype), []).append(i)
-            for (reg, _, _), members in by_region.items():
-                if len(members) > 1 and all(xs[i].shape[0] > 0 for i in members):
-                    lo, hi = reg
-                    r = ops.soft_vq_forward(torch.cat([xs[i].detach() for i in members]), what[lo:hi], wsq[lo:hi].contiguous(), topk, path, want_sqerr=True)
-                    a = 0
-                    for i in members:
-                        b = a + xs[i].shape[0]
-                        stacked[i] = {k: (v[a:b] if torch.is_tensor(v) else v) for k, v in r.items()}
-                        a = b
-        for i, (x, (lo, hi)) in enumerate(zip(xs, regions)):
-            r = (batched[i] if batched is not None else stacked[i] if i in stacked else
-                 ops.soft_vq_forward(x.detach(), what[lo:hi], wsq[lo:hi].contiguous(), topk, path, want_sqerr=True))
-            n, d = x.shape
-            outs += [r["zq"], ops.sum_scale(r["row_sqerr"], (1.0 / (n * d)) if n else float("nan")), ops.sum_scale(r["row_sqerr"], beta / (n * d) if n else float("nan")),
-                     r["xhat"], r["idx"], r["w"]]
-            saved += [x, r["xhat"], r["idx"], r["w"]]
-            nondiff += [r["idx"], r["w"]]
-        ctx.save_for_backward(weight, what, *saved)
-        ctx.regions, ctx.beta, ctx.m = tuple(regions), beta, len(xs)
-        ctx.mark_non_differentiable(*nondiff)
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        weight, what, *saved = ctx.saved_tensors
-        want_w = ctx.needs_input_grad[0]
-        as_f32 = lambda t: None if t is None else t.float()
-        gxs, g_codes, ids = [], [], []
-        for i in range(ctx.m):
-            x, xhat, idx, w = saved[4 * i: 4 * i + 4]
-            lo, hi = ctx.regions[i]
-            g_zq, g_vq, g_commit, g_xhat = grads[6 * i: 6 * i + 4]
-            n, d = x.shape
-            gx, g_code = ops.soft_vq_backward(x.detach(), xhat, what[lo:hi], idx, w, g_xhat=as_f32(g_xhat), g_out=as_f32(g_zq), g_vq=as_f32(g_vq),
-                                              g_commit=as_f32(g_commit), vq_scale=2.0 / (n * d), commit_scale=2.0 * ctx.beta / (n * d),
-                                              want_gx=ctx.needs_input_grad[7 + i], want_g_code=want_w)
-            gxs.append(gx)
-            if want_w and n:
-                g_codes.append(g_code)
-                ids.append(idx.reshape(-1) + lo if lo else idx.reshape(-1))
-        gw = None
-        if want_w:
-            if g_codes:
-                bins, g_what = ops.ema_stats(torch.cat(g_codes), torch.cat(ids), what.shape[0])
-                # (codes no row selected: bins = 0, their gradient rows are zeros -- written without reading the codebook)
-                gw = ops.normalize_backward(g_what, what, weight.detach(), live=bins)
-            else:
-                gw = torch.zeros_like(weight)
-        return (gw, None, None, None, None, None, None, *gxs)
 
 
 class _Norm(tuple):
@@ -1750,14 +1150,14 @@ class VectorQuantizer(nn.Module):
         split-fp16 product (medtok_split_gemm_f16: fp32-accurate, ~2.5x the library fp32 GEMM; weights split once per weight
         version) -- anything else (training, autograd, autocast, small batches, CPU): the nn.Linear as it stands."""
         lin = self.proj_text if types == "text" else self.proj_graph
-        if (SPLIT_PRODUCTS and TRAIN_SPLIT_PRODUCTS and self.training and torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 and lin.bias is not None
+        if (SPLIT_PRODUCTS and self.training and torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 and lin.bias is not None
                 and lin.in_features % 4 == 0 and lin.out_features % 4 == 0 and (x.requires_grad or lin.weight.requires_grad)):
             return split_linear(x, lin.weight, lin.bias)        # under autograd: forward and backward on the library's own product
         # (inference: fp32-accurate whatever autocast says -- an autocast caller's half-precision rows are widened, like fp16 tensors)
         if not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16):
             x = x.float()
         if (not SPLIT_PRODUCTS or self.training or torch.is_grad_enabled() or not x.is_cuda
-                or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] < SPLIT_MIN_ROWS or lin.bias is None
+                or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] == 0 or lin.bias is None
                 or lin.in_features % 32 or lin.out_features % 4 or x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16):
             return lin(x)
         key = (lin.weight.data_ptr(), lin.weight._version, lin.bias.data_ptr(), lin.bias._version, lin.weight.device)
@@ -2031,7 +1431,7 @@ class VectorQuantizer(nn.Module):
         """forward() in training mode under autograd with a trainable codebook: the cross-attention, then ALL searches under one
         autograd node (_SoftVQMultiFunction: one dense codebook gradient instead of six), then all usage-window updates in one call.
         Same values as the general form below; None when it does not apply."""
-        if not (TRAIN_SINGLE_CODEBOOK_GRADIENT and self.training and torch.is_grad_enabled() and z.is_cuda and z.shape[0] > 0
+        if not (self.training and torch.is_grad_enabled() and z.is_cuda and z.shape[0] > 0
                 and self.codebook.weight.requires_grad and self.e_dim % 4 == 0):
             return None
         what, wsq = norm

@@ -167,12 +167,13 @@ def test_key_gradient_sink_gives_the_gradients_of_plain_autograd(dev, autocast):
     order of the three-term sums on the CLS rows differs).  Also: a use of the text tensor outside the protocol, a backward that
     does not reach the text (torch.autograd.grad for the nodes alone) followed by a full one, and two backwards of one graph."""
     import contextlib
+    import medtok_amd.autograd as agmod
     import medtok_amd.vector_quantization_soft_one_new as vqmod
     ca, text0, mask, nodes0, batch, (pa, pb, pc) = _pooled_case(dev)
 
     def run(sink, mode):
-        old = vqmod.KEY_GRADIENT_SINK
-        vqmod.KEY_GRADIENT_SINK = sink
+        old = agmod.KEY_GRADIENT_SINK
+        agmod.KEY_GRADIENT_SINK = sink
         try:
             ca.zero_grad(set_to_none=True)
             text, nodes = text0.clone().requires_grad_(), nodes0.clone().requires_grad_()
@@ -201,7 +202,7 @@ def test_key_gradient_sink_gives_the_gradients_of_plain_autograd(dev, autocast):
                 loss.backward()
             return [text.grad.clone(), nodes.grad.clone()] + [p.grad.clone() for p in ca.parameters()]
         finally:
-            vqmod.KEY_GRADIENT_SINK = old
+            agmod.KEY_GRADIENT_SINK = old
     ref = run(False, "plain")
     assert float(ref[0].abs().max()) > 0 and float(ref[0][:, 2:].abs().max()) > 0      # the key gradients are there
     for mode in ("plain", "fan-first", "partial-then-full", "twice"):
@@ -215,6 +216,7 @@ def test_tokenizer_training_forward_maps_only_the_cls_row_of_the_aug_text(dev):
     """MultimodalTokenizer.forward in training: the aug text view is only read at its CLS row (reference tokenizer.py:163), so only that
     row goes through text_mapped; the CLS rows of the main view come from the gradient fan-out.  Outputs and the gradients of
     text_mapped / the codebook equal the form that maps every token of both views (sink off, full aug map)."""
+    import medtok_amd.autograd as agmod
     import medtok_amd.vector_quantization_soft_one_new as vqmod
     from medtok_amd import loss as L
     from medtok_amd.tokenizer import MultimodalTokenizer, make_inputs
@@ -234,10 +236,10 @@ def test_tokenizer_training_forward_maps_only_the_cls_row_of_the_aug_text(dev):
             mod.p = 0.0
         if isinstance(mod, nn.MultiheadAttention):
             mod.dropout = 0.0
-    old = (vqmod.KEY_GRADIENT_SINK, vqmod.TRAIN_SPLIT_TEXT_MAPPING)
+    old = (agmod.KEY_GRADIENT_SINK, vqmod.TRAIN_SPLIT_TEXT_MAPPING)
 
     def run(sink, full_aug):
-        vqmod.KEY_GRADIENT_SINK, vqmod.TRAIN_SPLIT_TEXT_MAPPING = sink, True
+        agmod.KEY_GRADIENT_SINK, vqmod.TRAIN_SPLIT_TEXT_MAPPING = sink, True
         model.zero_grad(set_to_none=True)
         inputs.graph_node_features.grad = inputs.graph_node_features_aug.grad = None
         if full_aug:                                   # the reference's form: every token of the aug view through the Linear
@@ -259,7 +261,7 @@ def test_tokenizer_training_forward_maps_only_the_cls_row_of_the_aug_text(dev):
         loss_ref, ref = run(False, True)
         loss_new, got = run(True, False)
     finally:
-        vqmod.KEY_GRADIENT_SINK, vqmod.TRAIN_SPLIT_TEXT_MAPPING = old
+        agmod.KEY_GRADIENT_SINK, vqmod.TRAIN_SPLIT_TEXT_MAPPING = old
     assert abs(loss_new - loss_ref) <= 1e-5 * abs(loss_ref)
     for a, b in zip(got, ref):
         assert float((a - b).abs().max()) <= 1e-5 * max(float(b.abs().max()), 1e-6)
@@ -301,7 +303,7 @@ def test_batched_training_searches_switch_gives_the_same_bits(dev):
     """TRAIN_BATCHED_SEARCHES (off by default: slower at BASELINE's codebook sizes): all searches of a training forward in one batched call
     (ops.soft_vq_forward_multi with per-row squared errors) -- every output of VectorQuantizer.forward and every gradient bit for bit
     those of the search-by-search form."""
-    import medtok_amd.vector_quantization_soft_one_new as vqmod
+    import medtok_amd.autograd as agmod
     from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer
     torch.manual_seed(2)
     bsz, seq_len, d = 9, 12, 128
@@ -320,8 +322,8 @@ def test_batched_training_searches_switch_gives_the_same_bits(dev):
     state = {k: v.clone() for k, v in vq.state_dict().items()}
 
     def run(batched):
-        old = vqmod.TRAIN_BATCHED_SEARCHES
-        vqmod.TRAIN_BATCHED_SEARCHES = batched
+        old = agmod.TRAIN_BATCHED_SEARCHES
+        agmod.TRAIN_BATCHED_SEARCHES = batched
         try:
             vq.load_state_dict(state)
             vq.zero_grad(set_to_none=True)
@@ -333,17 +335,17 @@ def test_batched_training_searches_switch_gives_the_same_bits(dev):
             outs = [loss.detach().clone(), r["shared_text_tokens"].clone(), r["text_tokens_weights"].clone(), r["specific_embedding_text"].detach().clone()]
             return outs + [zz.grad.clone(), text.grad.clone(), nodes.grad.clone(), vq.codebook.weight.grad.clone()]
         finally:
-            vqmod.TRAIN_BATCHED_SEARCHES = old
+            agmod.TRAIN_BATCHED_SEARCHES = old
     a, b = run(False), run(True)
     for x, y in zip(a, b):
         assert torch.equal(x, y)
     # ... and TRAIN_STACK_SEARCHES_OF_A_REGION (the searches of one region on their rows stacked; on by default): the same bits as off
-    keep = vqmod.TRAIN_STACK_SEARCHES_OF_A_REGION
+    keep = agmod.TRAIN_STACK_SEARCHES_OF_A_REGION
     try:
-        vqmod.TRAIN_STACK_SEARCHES_OF_A_REGION = False
+        agmod.TRAIN_STACK_SEARCHES_OF_A_REGION = False
         c = run(False)
     finally:
-        vqmod.TRAIN_STACK_SEARCHES_OF_A_REGION = keep
+        agmod.TRAIN_STACK_SEARCHES_OF_A_REGION = keep
     for x, y in zip(a, c):
         assert torch.equal(x, y)
 

@@ -9,18 +9,15 @@ from medtok_amd import ops
 import medtok_amd.vector_quantization_soft_one_new as vq
 variants = {
     "shipped": {},
-    "text_front": dict(TEXT_CHAIN_AFTER_LAYER=-1),
-    "text_behind_1": dict(TEXT_CHAIN_AFTER_LAYER=1),
     "prio_equal": dict(STREAM_PRIORITY=(0, 0, 0)),
     "images_high": dict(STREAM_PRIORITY=(-1, 0, -1)),
     "searches_high": dict(STREAM_PRIORITY=(-1, -1, 0)),
-    "no_lpt": dict(LPT_ORDER=False),
     "one_stream": dict(SIDE_STREAM_MIN_CODES=0),
-    "att0": dict(ATTENTION_VARIANT=0),
-    "att0_one_stream": dict(ATTENTION_VARIANT=0, SIDE_STREAM_MIN_CODES=0),
 }
 name = sys.argv[1]
-for k, v in variants[name].items(): setattr(vq, k, v)
+for k, v in variants[name].items():
+    assert hasattr(vq, k), k
+    setattr(vq, k, v)
 dev = torch.device("cuda:0")
 w = bench.Full(4096, dev, 0, ops.PATH_AUTO)
 def run(steps=10):

@@ -20,7 +20,7 @@ def diff(a, b, tag):
             print("   ", k, "max abs diff %.3e  rows differing %d of %d" % (float(d.max()), int((d.reshape(d.shape[0], -1).max(1).values > 0).sum()), d.shape[0]))
         else:
             print("   ", k, "rows differing", int((x != y).reshape(x.shape[0], -1).any(1).sum()))
-for name, setting in (("shipped", {}), ("att0", dict(ATTENTION_VARIANT=0)), ("one_stream", dict(SIDE_STREAM_MIN_CODES=0))):
+for name, setting in (("shipped", {}), ("one_stream", dict(SIDE_STREAM_MIN_CODES=0))):
     keep = {k: getattr(vq, k) for k in setting}
     for k, v in setting.items(): setattr(vq, k, v)
     a1, a2 = outs(ops.PATH_AUTO), outs(ops.PATH_AUTO)
