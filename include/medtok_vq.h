@@ -236,6 +236,39 @@ int medtok_decode_tokens_backward_f32(const float *g_out, int64_t g_stride, cons
                                       int slots, int topk, const float *what, int64_t n_codes, int d, const int64_t *region_lo,
                                       const int64_t *region_size, float *g_w, float *g_code, int64_t *g_ids, int *status, void *stream);
 
+/* ---- embedding lookup over the stored token table: code indices -> embedding -------------------------------
+ * What a downstream model does with embeddings_all.npy -- a [num_codes + 1, slots * d] table (the last row a learned "missing code"
+ * row) indexed by a [B, L] batch of code indices, padded positions masked (MedTok_EHR_Tutorial/EHRModel_token.py:128-141,214-215,
+ * dataloader.py:79-88) -- without the table: ONE launch goes from index [n] (int64, the flattened batch) through tokens / weights
+ * [num_codes, slots, topk] (tokens_all.npy / weights_all.npy as they are, region-local ids) to out [n, slots * d]; no gathered copies
+ * of the id and weight rows are made.  Per position p with c = index[p]:
+ *   pad[p] != 0  (pad: uint8 [n] or NULL)   the row is zeros; index[p] is not interpreted, no table is read, status is not touched
+ *   0 <= c < num_codes                      block s = sum_j weights[c, s, j] * what[region_lo[s] + tokens[c, s, j]]: the fp32 chain of
+ *                                           medtok_decode_tokens_f32, the same bits as that call on the gathered rows; a slot with an
+ *                                           id outside its region is zeros and sets bit s of *status, as there
+ *   c == num_codes and miss != NULL         a copy of miss [slots * d] (fp32), bit for bit
+ *   anything else                           the row is zeros and bit 4 of *status is set
+ * No index and no id is used as an address before it is checked; nothing traps and nothing is read back.  what, n_codes, d, the
+ * regions, out_stride (in elements of out, 0 = slots * d) and status are medtok_decode_tokens_f32's.
+ * Half-precision output is a SIBLING entry, medtok_embed_codes_f16 (bf16 != 0: bf16), not an enum argument on one function: the element
+ * type of `out` stays visible in the prototype, and `_f32` in a name keeps meaning fp32 results, as everywhere in this header (the
+ * 16-bit producers above take the same `bf16` flag).  Each element of the finished fp32 chain is rounded once, to nearest even: the
+ * result equals the fp32 result converted afterwards; out is then 8-byte aligned. */
+int medtok_embed_codes_f32(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                           int64_t num_codes, int slots, int topk, const float *what, int64_t n_codes, int d,
+                           const int64_t *region_lo, const int64_t *region_size, const float *miss, float *out, int64_t out_stride,
+                           int *status, void *stream);
+int medtok_embed_codes_f16(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                           int64_t num_codes, int slots, int topk, const float *what, int64_t n_codes, int d,
+                           const int64_t *region_lo, const int64_t *region_size, const float *miss, void *out, int64_t out_stride,
+                           int bf16, int *status, void *stream);
+/* The gradient of the miss row: g_miss[width] = sum of g_out[p, :] (fp32 [n, width], row stride g_stride, 0 = width) over the positions
+ * with index[p] == num_codes and pad[p] == 0, added in a fixed order (per 256 consecutive positions in position order, then those
+ * partial sums in order; no float atomics): two runs give the same bits.  ws from the workspace query. */
+size_t medtok_embed_codes_miss_grad_workspace_bytes(int64_t n, int width);
+int medtok_embed_codes_miss_grad_f32(const float *g_out, int64_t g_stride, const int64_t *index, const uint8_t *pad, int64_t n,
+                                     int64_t num_codes, int width, float *g_miss, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- fp32-accurate dense products on the fp16 matrix pipe (the projections around the cross-attention core:
  * nn.MultiheadAttention's in_proj / out_proj and the folded W_k / W_v products, vector_quantization_soft_one_new.py:17-51).
  * Every operand is a PAIR of fp16 images (hi, lo) with x = hi + lo; a product runs as three fp16 MFMA passes

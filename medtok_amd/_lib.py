@@ -74,6 +74,10 @@ SIGNATURES = {
     "medtok_sum_scale_f32": (_int, [_vp, _i64, _dbl, _vp, _vp]),
     "medtok_decode_tokens_f32": (_int, [_vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp]),
     "medtok_decode_tokens_backward_f32": (_int, [_vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "medtok_embed_codes_f32": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "medtok_embed_codes_f16": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp]),
+    "medtok_embed_codes_miss_grad_workspace_bytes": (_sz, [_i64, _int]),
+    "medtok_embed_codes_miss_grad_f32": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
     "medtok_soft_vq_backward_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     "medtok_normalize_backward_f32": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp]),
     "medtok_normalize_backward_sparse_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _vp, _vp]),

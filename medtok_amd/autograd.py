@@ -8,7 +8,8 @@ VectorQuantizer) and the tokenizer call it, and that module re-exports every nam
   - fan_out_text / _TextFanOut / _KeyGradSink: the text rows of a training step behind ONE gradient buffer;
   - _SegmentMeanFunction, _HeadBlockDiag: the node mean of a code, the block-diagonal per-head weights;
   - _SoftVQFunction / _SoftVQMultiFunction / _DecodeFunction: a search, all searches of a forward, and decode under autograd
-    (sparse backward; the code gradients summed per code without atomics).
+    (sparse backward; the code gradients summed per code without atomics);
+  - _EmbedCodesFunction: the embedding lookup over the stored token table (MedTokEmbedding) and the gradient of its miss row.
 """
 from __future__ import annotations
 
@@ -533,6 +534,26 @@ class _DecodeFunction(torch.autograd.Function):
         if g_w is not None:
             g_w = g_w.view(weights.shape)
         return g_w, gw, None, None, None, None
+
+
+class _EmbedCodesFunction(torch.autograd.Function):
+    """MedTokEmbedding.forward with a frozen codebook under autograd: the lookup kernel (medtok_embed_codes_*), whose one
+    differentiable input is the miss row.  Backward is the fixed-order sum of the upstream rows at the unpadded miss positions
+    (medtok_embed_codes_miss_grad_f32: no float atomics, two runs give the same bits); a half-precision upstream gradient is summed in
+    fp32."""
+
+    @staticmethod
+    def forward(ctx, miss, index, pad_mask, tokens, weights, what, regions, out_dtype, status):
+        out = ops.embed_codes(index, tokens, weights, what, regions, miss=miss.detach(), pad_mask=pad_mask, out_dtype=out_dtype, status=status)
+        ctx.save_for_backward(index, pad_mask)
+        ctx.num_codes = tokens.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        index, pad_mask = ctx.saved_tensors
+        g_miss = ops.embed_codes_miss_grad(g, index, ctx.num_codes, pad_mask) if ctx.needs_input_grad[0] else None
+        return g_miss, None, None, None, None, None, None, None, None
 
 
 def _lib_multi_max():

@@ -1933,6 +1933,82 @@ extern "C" int medtok_decode_tokens_backward_f32(const float *g_out, int64_t g_s
     return check_launch("decode_tokens_backward");
 }
 
+// ================================================================= embedding lookup: code indices -> stored tokens -> embedding
+#include "embed_kernels.h"
+
+// both output widths of medtok_embed_codes_*: decode's checks, then one launch
+template <typename OUT>
+static int embed_codes_launch(const char *fn, const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                              int64_t num_codes, int slots, int topk, const float *what, int64_t n_codes, int d, const int64_t *region_lo,
+                              const int64_t *region_size, const float *miss, OUT *out, int64_t out_stride, int *status, void *stream)
+{
+    DecodeRegions reg;
+    if (int rc = decode_args(fn, n, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
+    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
+    if (out_stride == 0) out_stride = (int64_t)slots * d;
+    if (out_stride < (int64_t)slots * d || (out_stride & 3)) return fail("%s: out_stride must be >= slots * d and a multiple of 4", fn);
+    if (n == 0) return 0;
+    if (!index || !tokens || !weights || !what || !out) return fail("%s: index, tokens, weights, what and out are required", fn);
+    const long items = (long)n * slots;
+    hipStream_t s = (hipStream_t)stream;
+#define MEDTOK_EMBED_LAUNCH(LANES, MAXK)                                                                                                    \
+    hipLaunchKernelGGL((embed_codes_kernel<LANES, MAXK, OUT>), dim3((unsigned)((items + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s, \
+                       index, pad, items, tokens, weights, (long)num_codes, slots, topk, what, d, reg, miss, out, (long)out_stride, status)
+    if (d <= 64) { if (topk <= 8) MEDTOK_EMBED_LAUNCH(16, 8); else MEDTOK_EMBED_LAUNCH(16, MEDTOK_MAX_TOPK); }
+    else         { if (topk <= 8) MEDTOK_EMBED_LAUNCH(64, 8); else MEDTOK_EMBED_LAUNCH(64, MEDTOK_MAX_TOPK); }
+#undef MEDTOK_EMBED_LAUNCH
+    return check_launch(fn);
+}
+
+extern "C" int medtok_embed_codes_f32(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                                      int64_t num_codes, int slots, int topk, const float *what, int64_t n_codes, int d,
+                                      const int64_t *region_lo, const int64_t *region_size, const float *miss, float *out, int64_t out_stride,
+                                      int *status, void *stream)
+{
+    return embed_codes_launch<float>("embed_codes", index, pad, n, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo, region_size,
+                                     miss, out, out_stride, status, stream);
+}
+
+extern "C" int medtok_embed_codes_f16(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                                      int64_t num_codes, int slots, int topk, const float *what, int64_t n_codes, int d,
+                                      const int64_t *region_lo, const int64_t *region_size, const float *miss, void *out, int64_t out_stride,
+                                      int bf16, int *status, void *stream)
+{
+    if (bf16)
+        return embed_codes_launch<__bf16>("embed_codes_f16(bf16)", index, pad, n, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo,
+                                          region_size, miss, (__bf16 *)out, out_stride, status, stream);
+    return embed_codes_launch<_Float16>("embed_codes_f16", index, pad, n, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo,
+                                        region_size, miss, (_Float16 *)out, out_stride, status, stream);
+}
+
+extern "C" size_t medtok_embed_codes_miss_grad_workspace_bytes(int64_t n, int width)
+{
+    if (n < 0 || width < 1) return 0;
+    const size_t chunks = (size_t)((n + MEDTOK_EMBED_GRAD_CHUNK - 1) / MEDTOK_EMBED_GRAD_CHUNK);
+    return (chunks * (size_t)width * sizeof(float) + 255) & ~(size_t)255;
+}
+
+extern "C" int medtok_embed_codes_miss_grad_f32(const float *g_out, int64_t g_stride, const int64_t *index, const uint8_t *pad, int64_t n,
+                                                int64_t num_codes, int width, float *g_miss, void *ws, size_t ws_bytes, void *stream)
+{
+    if (n < 0 || width < 1) return fail("embed_codes_miss_grad: bad shape n=%ld width=%d", (long)n, width);
+    if (g_stride == 0) g_stride = width;
+    if (g_stride < width) return fail("embed_codes_miss_grad: g_stride must be >= width");
+    if (!g_miss) return fail("embed_codes_miss_grad: g_miss is required");
+    if (n > 0 && (!g_out || !index)) return fail("embed_codes_miss_grad: g_out and index are required");
+    const long chunks = (long)((n + MEDTOK_EMBED_GRAD_CHUNK - 1) / MEDTOK_EMBED_GRAD_CHUNK);
+    if (chunks > 0x7fffffffl) return fail("embed_codes_miss_grad: n=%ld positions exceed one launch", (long)n);
+    if (chunks && (!ws || ws_bytes < medtok_embed_codes_miss_grad_workspace_bytes(n, width)))
+        return fail("embed_codes_miss_grad: workspace too small (%zu bytes given)", ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned col_blocks = (unsigned)((width + 255) / 256);
+    if (chunks)
+        hipLaunchKernelGGL(embed_miss_grad_partial_kernel, dim3((unsigned)chunks, col_blocks), dim3(256), 0, s, g_out, (long)g_stride, index, pad,
+                           (long)n, (long)num_codes, width, (float *)ws);
+    hipLaunchKernelGGL(embed_miss_grad_sum_kernel, dim3(col_blocks), dim3(256), 0, s, (const float *)ws, chunks, width, g_miss);
+    return check_launch("embed_codes_miss_grad");
+}
+
 // ================================================================= training half: sparse backward, normalize backward, InfoNCE
 #include "train_kernels.h"
 

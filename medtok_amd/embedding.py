@@ -1,0 +1,174 @@
+"""MedTokEmbedding: what a downstream model does with embeddings_all.npy, without the table.
+
+The reference's consumers load the [num_codes, 4 * e_dim] table onto the device, append a learned "missing code" row and index the
+result with a [B, max_medical_code] batch of code indices (MedTok_EHR_Tutorial/EHRModel_token.py:128-141,214-215; padding and
+code_mask in dataloader.py:79-88):
+
+    self.emb          = torch.from_numpy(np.load(pre_trained_embedding)).cuda()
+    self.miss_emb     = torch.nn.Parameter(torch.randn(1, 256)).cuda()
+    self.med_code_emb = torch.concat([self.emb, self.miss_emb], dim=0)
+    src_emb           = self.med_code_emb[data.x].squeeze()
+
+This module answers the same index tensor from tokens_all.npy / weights_all.npy (12 k bytes per code and slot instead of 4 e_dim)
+and a VectorQuantizer's codebook: one kernel goes from the indices through the stored ids and weights to the embedding
+(ops.embed_codes, medtok_amd/csrc/embed_kernels.h).  The one semantic difference: a position under the padding mask is a row of
+zeros, not code 0's embedding (the reference masks those positions in its attention anyway).
+"""
+from __future__ import annotations
+
+from pathlib import Path
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import ops
+from .autograd import _EmbedCodesFunction
+
+DEFAULT_TYPES = ("text", "graph", "shared", "shared")
+
+
+def _autocast_dtype():
+    """the dtype an active device autocast asks for, or None"""
+    if hasattr(torch, "get_autocast_dtype"):
+        return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
+    return torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None
+
+
+class MedTokEmbedding(nn.Module):
+    """`med_code_emb[index]` over the table `quantizer.decode(tokens, weights)` would build, plus a learned miss row.
+
+    quantizer: a VectorQuantizer; it is REFERENCED (its codebook is read on every call), not copied and not a submodule: it is
+    neither in this module's state dict nor moved by .to().  tokens int64 / weights fp32 [num_codes, S, k], numpy or tensor, slot s
+    searched over the region types[s]: persistent buffers (they travel in the state dict and with .to(); they start on the
+    codebook's device).  Ids are region-local as every forward returns them; global_ids=True takes rows of codebook.weight and
+    subtracts the region offsets once, here.  miss_row: keep `miss_emb`, an nn.Parameter [1, S * e_dim] initialised randn as the
+    reference's, served at index num_codes (`miss_index`); without it that index is an error.  freeze_codebook=True (the
+    reference's table is a constant): the only gradient is miss_emb's; False: codebook.weight gets its gradient too, where it
+    requires one (off the hot path: composed from quantizer.decode on the gathered rows)."""
+
+    def __init__(self, quantizer, tokens, weights, types=DEFAULT_TYPES, miss_row: bool = True, freeze_codebook: bool = True,
+                 global_ids: bool = False):
+        super().__init__()
+        kinds = (types,) if isinstance(types, str) else tuple(types)
+        if not 1 <= len(kinds) <= ops.DECODE_MAX_SLOTS or any(t not in quantizer.DECODE_TYPES for t in kinds):
+            raise ValueError(f"MedTokEmbedding: types must name 1 .. {ops.DECODE_MAX_SLOTS} of {quantizer.DECODE_TYPES}, got {types!r}")
+        dev = quantizer.codebook.weight.device
+        tokens = torch.as_tensor(np.ascontiguousarray(tokens) if isinstance(tokens, np.ndarray) else tokens)
+        weights = torch.as_tensor(np.ascontiguousarray(weights) if isinstance(weights, np.ndarray) else weights)
+        if tokens.dtype != torch.int64 or weights.dtype != torch.float32:
+            raise ValueError(f"MedTokEmbedding: expected int64 tokens and fp32 weights, got {tokens.dtype} and {weights.dtype}")
+        if tokens.dim() != 3 or tokens.shape != weights.shape or tokens.shape[1] != len(kinds) or tokens.shape[0] < 1:
+            raise ValueError(f"MedTokEmbedding: tokens and weights must both be [num_codes, {len(kinds)}, k] for types={types!r}; got "
+                             f"{tuple(tokens.shape)} and {tuple(weights.shape)}")
+        if not 1 <= tokens.shape[2] <= ops.MAX_TOPK:
+            raise ValueError(f"MedTokEmbedding: k={tokens.shape[2]} ids per slot unsupported (1 .. {ops.MAX_TOPK})")
+        self.__dict__["quantizer"] = quantizer            # (a plain attribute: nn.Module would register it as a submodule)
+        self.types = kinds
+        self.freeze_codebook = bool(freeze_codebook)
+        tokens = tokens.detach().to(dev, copy=True).contiguous()      # (copies: load_state_dict writes into the buffers in place)
+        if global_ids:
+            tokens -= torch.tensor([quantizer._region(t)[0] for t in kinds], dtype=torch.int64, device=dev).view(1, -1, 1)
+        self.register_buffer("tokens", tokens)
+        self.register_buffer("weights", weights.detach().to(dev, copy=True).contiguous())
+        self.num_codes = int(tokens.shape[0])
+        self.embedding_dim = len(kinds) * int(quantizer.e_dim)
+        self.miss_index = self.num_codes if miss_row else None
+        self.num_embeddings = self.num_codes + (1 if miss_row else 0)
+        if miss_row:
+            self.miss_emb = nn.Parameter(torch.randn(1, self.embedding_dim, device=dev))
+        else:
+            self.register_parameter("miss_emb", None)
+
+    @classmethod
+    def from_dir(cls, path, quantizer, **kw):
+        """From the arrays run_inference wrote; reads tokens_all.npy and weights_all.npy only (never embeddings_all.npy)."""
+        p = Path(path)
+        return cls(quantizer, np.load(p / "tokens_all.npy"), np.load(p / "weights_all.npy"), **kw)
+
+    def extra_repr(self):
+        return (f"num_embeddings={self.num_embeddings}, embedding_dim={self.embedding_dim}, k={self.tokens.shape[2]}, types={self.types}, "
+                f"freeze_codebook={self.freeze_codebook}")
+
+    def _regions(self):
+        return [(lo, hi - lo) for lo, hi in (self.quantizer._region(t) for t in self.types)]
+
+    def forward(self, index, padding_mask=None, validate: bool = True, out_dtype=None, out=None):
+        """index int64 [...] -> [..., S * e_dim].  padding_mask: bool / uint8 of index's shape, True = padded (the sense of the
+        reference's code_mask): those rows are zeros whatever the index holds.  Without a mask and in fp32 the result is what
+        `med_code_emb[index]` gives over the decoded table.
+
+        validate=True reads ONE status word back and raises ValueError naming the "code index" (an unmasked index outside
+        [0, num_embeddings)) or the first slot of the table that holds a token id outside its region; validate=False reads nothing
+        (such rows are zeros), so the call can be captured in a HIP graph.  out_dtype: torch.float32 / float16 / bfloat16; None =
+        fp32, or the autocast dtype where autocast is active.  `out`: a [index.numel(), S * e_dim] device view of that dtype to fill
+        (e.g. a column block of a wider tensor); such a call is not differentiable."""
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+            raise ValueError(f"MedTokEmbedding: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+        if out_dtype is None:
+            out_dtype = (out.dtype if out is not None else None) or _autocast_dtype() or torch.float32
+        if out_dtype not in ops.EMBED_OUT_DTYPES:
+            raise ValueError(f"MedTokEmbedding: out_dtype must be one of {ops.EMBED_OUT_DTYPES}, got {out_dtype!r}")
+        padding_mask = ops._embed_mask("MedTokEmbedding", padding_mask, index)
+        q = self.quantizer
+        s, e, pad = len(self.types), int(q.e_dim), getattr(q, "_pad", 0)
+        n = index.numel()
+        if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == out_dtype and tuple(out.shape) == (n, s * e)):
+            raise ValueError(f"MedTokEmbedding: out must be a {out_dtype} [{n}, {s * e}] tensor")
+        grad_on = out is None and torch.is_grad_enabled()
+        want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
+        if want_codebook:
+            return self._forward_composed(index, padding_mask, validate, out_dtype)
+        regions = self._regions()
+        what = q._normalised_codebook()[0]
+        miss = self.miss_emb
+        want_miss = grad_on and miss is not None and miss.requires_grad
+        if miss is not None:
+            if not want_miss:
+                miss = miss.detach()
+            miss = (torch.nn.functional.pad(miss.view(s, e), (0, pad)) if pad else miss).reshape(-1)
+        status = torch.zeros(1, dtype=torch.int32, device=self.tokens.device) if validate else None
+        if want_miss:
+            res = _EmbedCodesFunction.apply(miss, index, padding_mask, self.tokens, self.weights, what, tuple(regions), out_dtype, status)
+        else:
+            res = ops.embed_codes(index, self.tokens, self.weights, what, regions, miss=miss, pad_mask=padding_mask,
+                                  out=None if pad else out, out_dtype=out_dtype, status=status)
+        if pad:
+            res = res.reshape(n, s, e + pad)[:, :, :e].reshape(n, s * e)
+            if out is not None:
+                out.copy_(res)
+        if validate:
+            self._raise_on(int(status.item()), regions)
+        return out if out is not None else res.reshape(*index.shape, s * e)
+
+    def _raise_on(self, word, regions):
+        if not word:
+            return
+        if word >> ops.EMBED_BAD_INDEX_BIT & 1:
+            raise ValueError(f"MedTokEmbedding: a code index outside [0, {self.num_embeddings}) at a position the padding mask does not cover"
+                             + ("" if self.miss_index is not None else f" (no miss row: {self.num_codes} is not an index)"))
+        bad = (word & -word).bit_length() - 1
+        raise ValueError(f"MedTokEmbedding: slot {bad} ({self.types[bad]!r}) of the token table holds an id outside [0, {regions[bad][1]}); "
+                         f"slots with bad ids: {[i for i in range(len(regions)) if word >> i & 1]}")
+
+    def _forward_composed(self, index, padding_mask, validate, out_dtype):
+        """freeze_codebook=False: the same function with a gradient for codebook.weight, from quantizer.decode's autograd on the
+        gathered rows of the live positions (torch gathers, boolean indexing and a host read: not the hot path)."""
+        padding_mask = ops._embed_mask("MedTokEmbedding", padding_mask, index)
+        flat = index.reshape(-1)
+        if not flat.is_cuda:
+            ops._dev(flat, "index", torch.int64)
+        padded = torch.zeros_like(flat, dtype=torch.bool) if padding_mask is None else padding_mask.reshape(-1).to(flat.device) != 0
+        live = ~padded & (flat >= 0) & (flat < self.num_codes)
+        is_miss = ~padded & (flat == self.num_codes) if self.miss_emb is not None else torch.zeros_like(padded)
+        if validate and bool((~(padded | live | is_miss)).any()):
+            self._raise_on(1 << ops.EMBED_BAD_INDEX_BIT, None)
+        out = torch.zeros(flat.numel(), self.embedding_dim, dtype=torch.float32, device=flat.device)
+        at = live.nonzero().squeeze(1)
+        if at.numel():
+            sel = flat[at]
+            out = out.index_put((at,), self.quantizer.decode(self.tokens[sel], self.weights[sel], types=self.types, validate=validate))
+        at = is_miss.nonzero().squeeze(1)
+        if at.numel():
+            out = out.index_put((at,), self.miss_emb.expand(at.numel(), -1))
+        return out.to(out_dtype).reshape(*index.shape, self.embedding_dim)

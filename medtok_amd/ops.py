@@ -264,6 +264,12 @@ DECODE_MAX_SLOTS = _lib.DECODE_MAX_SLOTS
 def _decode_args(fn, tokens, weights, what, regions, g_out=None):
     """shared checks of decode_tokens / decode_tokens_backward: shapes and regions raise ValueError before any library call; tensors
     that are not on the device raise MedTokLibraryError (_dev).  Returns (tokens [n, s, k], weights, what, lo[], size[])."""
+    tokens, weights, regions = _decode_shapes(fn, tokens, weights, what, regions, g_out)
+    return _decode_on_device(tokens, weights, what, regions)
+
+
+def _decode_shapes(fn, tokens, weights, what, regions, g_out=None):
+    """the ValueError half of _decode_args: (tokens [n, s, k], weights [n, s, k], [(lo, size)] per slot); nothing is moved or loaded"""
     if not isinstance(tokens, torch.Tensor) or not isinstance(weights, torch.Tensor) or not isinstance(what, torch.Tensor):
         raise ValueError(f"{fn}: tokens, weights and what must be tensors")
     if tokens.dtype != torch.int64 or weights.dtype != torch.float32 or what.dtype != torch.float32:
@@ -285,9 +291,14 @@ def _decode_args(fn, tokens, weights, what, regions, g_out=None):
             raise ValueError(f"{fn}: region [{lo}, +{size}) is not inside the {what.shape[0]} codes")
     if g_out is not None and (not isinstance(g_out, torch.Tensor) or g_out.dtype != torch.float32 or g_out.shape != (n, s * what.shape[1])):
         raise ValueError(f"{fn}: g_out must be fp32 [{n}, {s * what.shape[1]}]")
+    return tokens, weights, regions
+
+
+def _decode_on_device(tokens, weights, what, regions):
+    """the device half of _decode_args: contiguous device tensors (MedTokLibraryError for anything else) and the regions as C arrays"""
     tokens, weights, what = _dev(tokens, "tokens", torch.int64), _dev(weights, "weights"), _dev(what, "what")
     import ctypes as C
-    arr = C.c_int64 * s
+    arr = C.c_int64 * len(regions)
     return tokens, weights, what, arr(*[r[0] for r in regions]), arr(*[r[1] for r in regions])
 
 
@@ -338,6 +349,107 @@ def decode_tokens_backward(g_out, tokens, weights, what, regions=None, want_g_w:
                                                          what.data_ptr(), what.shape[0], d, los, sizes, _ptr(g_w), _ptr(g_code), _ptr(g_ids),
                                                          _ptr(status), _stream(what)), "medtok_decode_tokens_backward_f32")
     return g_w, g_code, g_ids
+
+
+EMBED_BAD_INDEX_BIT = 4
+EMBED_OUT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _embed_mask(fn, pad_mask, index):
+    """pad_mask (bool or uint8, the shape of index, True / non-zero = padded) as a flat uint8 view, or None"""
+    if pad_mask is None:
+        return None
+    if not isinstance(pad_mask, torch.Tensor) or pad_mask.dtype not in (torch.bool, torch.uint8) or pad_mask.shape != index.shape:
+        raise ValueError(f"{fn}: pad_mask must be a bool or uint8 tensor of index's shape {tuple(index.shape)}, got "
+                         f"{getattr(pad_mask, 'dtype', type(pad_mask))} {tuple(getattr(pad_mask, 'shape', ()))}")
+    return pad_mask
+
+
+def _embed_mask_on_device(pad_mask):
+    if pad_mask is None:
+        return None
+    if not pad_mask.is_cuda:
+        _dev(pad_mask, "pad_mask", pad_mask.dtype)
+    pad_mask = pad_mask.contiguous()
+    return pad_mask.view(torch.uint8) if pad_mask.dtype == torch.bool else pad_mask
+
+
+def embed_codes(index, tokens, weights, what, regions=None, miss=None, pad_mask=None, out=None, out_dtype=torch.float32, status=None):
+    """Embeddings of code indices straight from the stored token table: what `table[index]` gives over the table
+    decode_tokens(tokens, weights, ...) would build (plus a miss row), in one launch and without the table -> [*index.shape, slots * d].
+
+    index int64, any shape; tokens int64 / weights fp32 [num_codes, slots, k] (region-local ids); what, regions: as decode_tokens.
+    miss: fp32 [slots * d] (or [1, slots * d]), the row of index == num_codes, or None; pad_mask: bool / uint8 of index's shape,
+    True = padded.  Padded positions are zeros whatever their index holds; an index in [0, num_codes) gives the bits of decode_tokens
+    on that code's rows; num_codes gives `miss`; any other index gives zeros and sets bit 4 of `status` (an int32 device tensor of one
+    ZEROED element, or None; bit s: slot s of some code held an id outside its region) -- nothing is read back here.
+    out_dtype: torch.float32, float16 or bfloat16 (the fp32 result rounded once to nearest even: equal to `.to(out_dtype)` of it).
+    `out`: a [index.numel(), slots * d] device view of that dtype with unit column stride, e.g. a column block of a wider tensor."""
+    fn = "embed_codes"
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+    if out_dtype not in EMBED_OUT_DTYPES:
+        raise ValueError(f"{fn}: out_dtype must be one of {EMBED_OUT_DTYPES}, got {out_dtype!r}")
+    pad_mask = _embed_mask(fn, pad_mask, index)
+    tokens, weights, regions = _decode_shapes(fn, tokens, weights, what, regions)
+    num_codes, s, k = tokens.shape
+    if num_codes < 1:
+        raise ValueError(f"{fn}: the token table is empty")
+    d = what.shape[1]
+    n, width = index.numel(), s * d
+    if miss is not None and (not isinstance(miss, torch.Tensor) or miss.dtype != torch.float32 or miss.numel() != width or miss.dim() not in (1, 2)
+                             or miss.shape[-1] != width):
+        raise ValueError(f"{fn}: miss must be fp32 [{width}] or [1, {width}], got {getattr(miss, 'dtype', type(miss))} "
+                         f"{tuple(getattr(miss, 'shape', ()))}")
+    if out is not None:
+        align = 16 if out_dtype == torch.float32 else 8
+        if not (isinstance(out, torch.Tensor) and out.dtype == out_dtype and tuple(out.shape) == (n, width) and out.stride(1) == 1
+                and out.stride(0) % 4 == 0 and out.data_ptr() % align == 0):
+            raise ValueError(f"{fn}: out must be a {out_dtype} [{n}, {width}] view with unit column stride and {align}-byte aligned rows")
+    index = _dev(index, "index", torch.int64)
+    tokens, weights, what, los, sizes = _decode_on_device(tokens, weights, what, regions)
+    miss = None if miss is None else _dev(miss, "miss")
+    pad_mask = _embed_mask_on_device(pad_mask)
+    if out is not None and not out.is_cuda:
+        _dev(out, "out", out_dtype)
+    if status is not None:
+        status = _dev(status, "status", torch.int32)
+    res = torch.empty((n, width), dtype=out_dtype, device=what.device) if out is None else out
+    stride = res.stride(0) if n else 0
+    lib = _lib.load()
+    with _on(what.device):
+        head = (index.data_ptr(), _ptr(pad_mask), n, tokens.data_ptr(), weights.data_ptr(), num_codes, s, k, what.data_ptr(), what.shape[0], d,
+                los, sizes, _ptr(miss), res.data_ptr(), stride)
+        if out_dtype == torch.float32:
+            _lib.check(lib.medtok_embed_codes_f32(*head, _ptr(status), _stream(what)), "medtok_embed_codes_f32")
+        else:
+            _lib.check(lib.medtok_embed_codes_f16(*head, int(out_dtype == torch.bfloat16), _ptr(status), _stream(what)), "medtok_embed_codes_f16")
+    return res.view(*index.shape, width) if out is None else out
+
+
+def embed_codes_miss_grad(g_out, index, num_codes, pad_mask=None):
+    """Gradient of embed_codes' miss row: the fp32 sum [width] of g_out [*index.shape, width] over the positions with
+    index == num_codes that are not padded, added in a fixed order (no float atomics: two runs give the same bits).  A half-precision
+    g_out is converted to fp32 first."""
+    fn = "embed_codes_miss_grad"
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+    if (not isinstance(g_out, torch.Tensor) or g_out.dtype not in EMBED_OUT_DTYPES or g_out.dim() < 1
+            or g_out.numel() != index.numel() * g_out.shape[-1] or g_out.shape[-1] < 1):
+        raise ValueError(f"{fn}: g_out must be a floating [*{tuple(index.shape)}, width] tensor, got {tuple(getattr(g_out, 'shape', ()))}")
+    pad_mask = _embed_mask(fn, pad_mask, index)
+    index = _dev(index, "index", torch.int64)
+    pad_mask = _embed_mask_on_device(pad_mask)
+    width, n = g_out.shape[-1], index.numel()
+    g_out = _dev(g_out.float().reshape(n, width), "g_out")
+    g_miss = torch.empty(width, dtype=torch.float32, device=g_out.device)
+    lib = _lib.load()
+    ws = _ws(lib.medtok_embed_codes_miss_grad_workspace_bytes(n, width), g_out)
+    with _on(g_out.device):
+        _lib.check(lib.medtok_embed_codes_miss_grad_f32(g_out.data_ptr(), width, index.data_ptr(), _ptr(pad_mask), n, int(num_codes), width,
+                                                        g_miss.data_ptr(), ws.data_ptr(), ws.numel(), _stream(g_out)),
+                   "medtok_embed_codes_miss_grad_f32")
+    return g_miss
 
 
 def soft_vq_backward(x, xhat, what, idx, w, g_zq=None, g_xhat=None, g_out=None, g_vq=None, g_commit=None,

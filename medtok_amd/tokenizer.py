@@ -274,5 +274,13 @@ class MedTokLookup:
             out = self.embeddings[rows]
         return out[0] if single else out
 
+    def embedding_layer(self, **kw):
+        """An nn.Module serving this lookup's rows by integer index on the quantiser's device (embedding.MedTokEmbedding: index i is
+        codes[i], index len(self) the learned miss row): what a model trains on instead of the embedding table.  Needs a quantiser."""
+        if self.quantizer is None:
+            raise ValueError("MedTokLookup.embedding_layer: a quantizer is needed to decode embeddings from tokens and weights")
+        from .embedding import MedTokEmbedding
+        return MedTokEmbedding(self.quantizer, np.asarray(self.tokens, dtype=np.int64), np.asarray(self.weights, dtype=np.float32), **kw)
+
     def __len__(self):
         return len(self.codes)

@@ -1,0 +1,195 @@
+"""Time MedTokEmbedding -- code indices -> embeddings through the stored token table -- on one MI355X against the two ways a
+downstream model had before it.
+
+    python tools/bench_embed.py [--codes 600000] [--batch 32] [--length 3000] [--reps 20] [--warmup 3] [--out profiles/embed_bench.json]
+
+Prints ONE JSON line.  A [batch, length] index tensor over num_codes codes (S = 4 slots, k = 5), about 40 % of the positions under
+the padding mask and 1 % at the miss index, at two shapes: the reference's (e_dim 64, n_e 21000) and cfg 3 (e_dim 768, n_e 49152).
+Per shape:
+
+  kernel_f32 / kernel_bf16   MedTokEmbedding.forward(index, padding_mask, validate=False): one launch, fp32 or bf16 rows
+  composition                what the parent commit offered: quantizer.decode(tokens[idx], weights[idx]) on the gathered rows, the miss
+                             row put in with torch.where and the padded rows zeroed with masked_fill (no host read either)
+  table_gather               the reference's way: med_code_emb[index] over the materialised fp32 table with the miss row appended
+                             (EHRModel_token.py:128-141,214-215; its padded positions hold code 0's row).  The table has --table-rows
+                             rows (default: all num_codes where they fit into a quarter of the free memory, else as many as do; the
+                             indices are folded into them) -- `table_rows` in the result says how many
+
+Discipline (bench_decode.py's): all sides are warmed up at the timed shape, compared before anything is timed, timed with device
+events over samples of >= 50 ms of back-to-back calls that ALTERNATE between the sides, at least 20 samples each; the shader clock
+(ops.ClockProbe) is read over further kernel samples right behind the timed region.  Algorithmic bytes of the kernel = per position
+the index and the mask byte, per live position S * 12 k of ids and weights, per position the written row, plus the codebook once;
+their rate is given as a fraction of the 6.29 TB/s a float4 copy reaches on this chip (8.0 TB/s is the HBM3E spec).
+`device_bytes_held` is what each approach keeps resident between calls.
+"""
+from __future__ import annotations
+
+import argparse
+import datetime
+import json
+import math
+import statistics
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+HBM_MEASURED_TBS = 6.29       # float4 copy
+HBM_SPEC_TBS = 8.0
+SHAPES = {"reference": dict(d=64, n_e=21000), "cfg3": dict(d=768, n_e=49152)}
+TYPES = ("text", "graph", "shared", "shared")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--codes", type=int, default=600000)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--length", type=int, default=3000)
+    ap.add_argument("--k", type=int, default=5)
+    ap.add_argument("--padded", type=float, default=0.40)
+    ap.add_argument("--miss", type=float, default=0.01)
+    ap.add_argument("--table-rows", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--shapes", default="reference,cfg3")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.reps < 20:
+        ap.error("--reps must be at least 20")
+
+    import torch
+    from medtok_amd import MedTokEmbedding, ops
+    from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_embed needs an MI355X: there is nothing to time without one")
+    dev = torch.device("cuda:0")
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    def inner_for(fn):
+        t = timed(fn, 1)
+        return max(1, min(200, math.ceil(50.0 / max(t, 1e-3))))
+
+    def stats(ms):
+        return dict(ms_median=statistics.median(ms), ms_min=min(ms), ms_max=max(ms), ms_mean=statistics.fmean(ms), samples=len(ms))
+
+    result = {"tool": "tools/bench_embed.py", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
+              "num_codes": args.codes, "positions": [args.batch, args.length], "slots": 4, "k": args.k, "padded_fraction": args.padded,
+              "miss_fraction": args.miss, "hbm_roof_tb_s": HBM_MEASURED_TBS, "hbm_spec_tb_s": HBM_SPEC_TBS, "shapes": {}}
+    for name in args.shapes.split(","):
+        d, n_e = SHAPES[name]["d"], SHAPES[name]["n_e"]
+        k, num_codes, width = args.k, args.codes, 4 * SHAPES[name]["d"]
+        n_pos = args.batch * args.length
+        torch.manual_seed(0)
+        vq = VectorQuantizer(n_e, d, 0.25, 0.0, True, False, [d, d], k=k)
+        with torch.no_grad():
+            vq.codebook.weight.normal_()
+        vq = vq.to(dev).eval()
+        gen = torch.Generator(device=dev).manual_seed(1)
+        sizes = [hi - lo for lo, hi in (vq._region(t) for t in TYPES)]
+        tokens = torch.stack([torch.randint(0, s, (num_codes, k), generator=gen, device=dev) for s in sizes], 1).contiguous()
+        weights = torch.softmax(torch.randn(num_codes, 4, k, generator=gen, device=dev), -1).contiguous()
+        module = MedTokEmbedding(vq, tokens, weights).to(dev)
+        del tokens, weights
+        tokens, weights, miss = module.tokens, module.weights, module.miss_emb.detach()
+        index = torch.randint(0, num_codes, (args.batch, args.length), generator=gen, device=dev)
+        u = torch.rand(args.batch, args.length, generator=gen, device=dev)
+        index[u < args.miss] = num_codes
+        mask = u > 1.0 - args.padded
+        index[mask] = 0                                     # (the reference's dataloader pads with code 0 under its code_mask)
+        live = int((~mask & (index < num_codes)).sum())
+        n_miss = int((~mask & (index == num_codes)).sum())
+
+        # the reference's table: decoded in chunks, the miss row appended; as many rows as fit comfortably
+        free = torch.cuda.mem_get_info(dev)[0]
+        fit = int(free // 4 // (width * 4))
+        table_rows = min(num_codes, args.table_rows or fit)
+        table = torch.empty(table_rows + 1, width, device=dev)
+        with torch.no_grad():
+            for r0 in range(0, table_rows, 65536):
+                r1 = min(table_rows, r0 + 65536)
+                vq.decode(tokens[r0:r1], weights[r0:r1], out=table[r0:r1], validate=False)
+            table[table_rows] = miss[0]
+        table_index = torch.where(index == num_codes, table_rows, index % table_rows)
+        is_miss = (index == num_codes).unsqueeze(-1)
+        safe = torch.where(index < num_codes, index, 0).reshape(-1)
+        outs = {}
+
+        def kernel_f32():
+            outs["kernel_f32"] = module(index, padding_mask=mask, validate=False)
+
+        def kernel_bf16():
+            outs["kernel_bf16"] = module(index, padding_mask=mask, validate=False, out_dtype=torch.bfloat16)
+
+        def composition():
+            rows = vq.decode(tokens[safe], weights[safe], validate=False).view(args.batch, args.length, width)
+            outs["composition"] = torch.where(is_miss, miss[0], rows).masked_fill_(mask.unsqueeze(-1), 0.0)
+
+        def table_gather():
+            outs["table_gather"] = table[table_index]
+
+        sides = {"kernel_f32": kernel_f32, "kernel_bf16": kernel_bf16, "composition": composition, "table_gather": table_gather}
+        with torch.no_grad():
+            for _ in range(args.warmup):
+                for fn in sides.values():
+                    fn()
+            torch.cuda.synchronize()
+            if not torch.equal(outs["kernel_f32"], outs["composition"]):
+                raise SystemExit(f"{name}: kernel and torch composition disagree")
+            if not torch.equal(outs["kernel_bf16"], outs["kernel_f32"].to(torch.bfloat16)):
+                raise SystemExit(f"{name}: the bf16 output is not the rounded fp32 output")
+            if table_rows == num_codes and not torch.equal(outs["table_gather"][~mask], outs["kernel_f32"][~mask]):
+                raise SystemExit(f"{name}: kernel and table gather disagree on the unpadded positions")
+            inner = {s: inner_for(fn) for s, fn in sides.items()}
+            ms = {s: [] for s in sides}
+            for _ in range(args.reps):                      # the sides alternate
+                for s, fn in sides.items():
+                    ms[s].append(timed(fn, inner[s]))
+            with ops.ClockProbe(dev, max_seconds=10.0) as probe:
+                for _ in range(max(2, args.reps // 4)):
+                    timed(kernel_f32, inner["kernel_f32"])
+            clock = probe.result()
+        st = {s: stats(v) for s, v in ms.items()}
+        table_bytes = live * 4 * 12 * k + n_pos * 9 + n_e * d * 4
+        alg = {"kernel_f32": table_bytes + n_pos * width * 4, "kernel_bf16": table_bytes + n_pos * width * 2,
+               "table_gather": n_pos * 8 + 2 * n_pos * width * 4}
+        held = {"kernel": tokens.numel() * 8 + weights.numel() * 4 + 2 * n_e * d * 4 + width * 4,
+                "composition": tokens.numel() * 8 + weights.numel() * 4 + 2 * n_e * d * 4 + width * 4,
+                "table_gather": table.numel() * 4, "table_gather_at_all_codes": (num_codes + 1) * width * 4}
+        entry = {"d": d, "n_e": n_e, "k": k, "num_codes": num_codes, "positions": n_pos, "live_positions": live, "miss_positions": n_miss,
+                 "padded_positions": int(mask.sum()), "output_gb_f32": n_pos * width * 4 / 1e9, "table_rows": table_rows,
+                 "table_is_complete": table_rows == num_codes, "device_bytes_held": held,
+                 "composition_temporaries_bytes": n_pos * 4 * k * 12 + 2 * n_pos * width * 4,
+                 "clock_ghz": clock.get("ghz_mean"), "clock_ghz_min": clock.get("ghz_min"), "clock_ghz_max": clock.get("ghz_max"),
+                 "clock_region": "further kernel_f32 samples right behind the timed region"}
+        for s in sides:
+            e = dict(st[s], calls_per_sample=inner[s], positions_per_s=n_pos / (st[s]["ms_median"] * 1e-3))
+            if s in alg:
+                tbs = alg[s] / (st[s]["ms_median"] * 1e-3) / 1e12
+                e.update(algorithmic_bytes=alg[s], algorithmic_tb_s=tbs, frac_of_hbm_roof=tbs / HBM_MEASURED_TBS, frac_of_hbm_spec=tbs / HBM_SPEC_TBS)
+            entry[s] = e
+        entry["kernel_f32_speedup_over_composition"] = st["composition"]["ms_median"] / st["kernel_f32"]["ms_median"]
+        entry["kernel_f32_speedup_over_table_gather"] = st["table_gather"]["ms_median"] / st["kernel_f32"]["ms_median"]
+        entry["kernel_bf16_speedup_over_kernel_f32"] = st["kernel_f32"]["ms_median"] / st["kernel_bf16"]["ms_median"]
+        entry["kernel_at_least_as_fast_as_composition"] = st["kernel_f32"]["ms_median"] <= st["composition"]["ms_median"]
+        result["shapes"][name] = entry
+        del table, outs, module, tokens, weights, index, mask, table_index, safe, is_miss
+        torch.cuda.empty_cache()
+    line = json.dumps(result)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
