@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MEDTOK_VQ_ABI_VERSION 3
+#define MEDTOK_VQ_ABI_VERSION 4
 /* codes per row a search returns: 1 .. 16.  Lists of up to 8 run on either search path; 9 .. 16 (the reference takes any k,
  * vector_quantization_soft_one_new.py:91) always take the exact fp32 path, as two passes of lists of 8 (the 8 best, then the best
  * among the codes behind the row's 8th (distance, index) pair) -- the same total order as one list of k. */
@@ -416,19 +416,10 @@ int medtok_shared_kv_attention_split_f32(const float *q, const int64_t *q_start,
  * on its images) -- no image pass over the key batch, no image buffers. */
 #define MEDTOK_ATTENTION_F32_KEYS 0x100
 
-/* Dev probes (tools/r04/att_probe.py, tools/r04/filter_probe.py): per-wave cycle counts (s_memtime) of a kernel's loop segments,
- * written by a TIMED instantiation that only these entry points launch.  medtok_debug_set_attention_probe(p) arms the next
- * medtok_shared_kv_attention_split_f32 calls with variant = 2 | (8 << 4), d = 768 (uint64 [blocks][8 waves][8]; NULL disarms; the one
- * piece of process state besides the bench profiler); medtok_debug_filter_probe runs the filter kernel of one search
- * (uint64 [blocks][8][8]: MFMA group 1, wait for own copies, stage barrier, MFMA group 2, tile epilogue, stages, code tiles). */
-void medtok_debug_set_attention_probe(void *probe);
-/* DEV: bit 0 of `on`: run the one-pass half-precision products (medtok_half_gemm_f32) with 32-deep stages as before round 6 instead of
- * 64-deep ones; bit 1: give the dense products' tiles to the XCDs by row tile whatever the row-tile count (before round 6: a product of 3
- * row tiles ran on 3 of the 8 XCDs) -- the A/B switches of tools/r06/ab_half_gemm_k64.py; same results either way. */
+/* Test hook, the one piece of process state besides the bench profiler: on != 0 runs the one-pass half-precision products
+ * (medtok_half_gemm_f32) with 32-deep stages instead of 64-deep ones wherever the depth allows both; same bits either way
+ * (tests/test_gpu_split_gemm.py, tools/r06/ab_half_gemm_k64.py).  Only bit 0 of `on` is read. */
 void medtok_debug_set_half_gemm_k32(int on);
-int medtok_debug_filter_probe(const float *xhat, const float *xsq, int64_t n, const float *what, const float *wsq, int64_t k_codes,
-                              int d, int topk, void *ws, size_t ws_bytes, void *probe, size_t probe_bytes, int64_t *n_blocks,
-                              void *stream);
 
 /* CrossAttention over a whole batch at the reference's default width (vector_quantization_soft_one_new.py:17-88,133-142 with
  * e_dim = 64, num_head = 4: train_MedTok.py:363-368) in TWO launches and no host round trip: for every code b

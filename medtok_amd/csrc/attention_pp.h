@@ -44,8 +44,6 @@ struct AttPP {
 // bar of the attention outputs; expf()'s range reduction was a third of the softmax step.
 __device__ __forceinline__ float pp_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
-// TIMED (dev probe, tools/r04/att_probe.py through medtok_debug_set_attention_probe; the product instantiates TIMED = false): per-wave
-// cycle counts (s_memtime) of the three phases and of the waits between them, written to `dbg` (uint64 [blocks][8 waves][8]).
 // KLO = false: the keys are fp16 as they stand (a caller under fp16 autocast hands over half-precision text features, the
 // reference's default training mode train_MedTok.py:212,394): there is no lo image -- kvl is not read, a chunk is one plane (half
 // the bytes from HBM and through the DMA), and the passes against it drop out of both products (two MFMAs per step instead of
@@ -63,12 +61,12 @@ __device__ __forceinline__ float pp_exp(float x) { return __builtin_amdgcn_exp2f
 // normaliser is that of the full softmax, kept ones are scaled by keep_scale = 1 / (1 - p) -- and the log-sum-exp of every query row
 // for the backward kernels' softmax rebuild (attention_backward.h).  Same mask bits as the fp32 kernel (same hash of the same
 // (packed query row, key) pair); the three-pass products differ from its fp32 ones by ~2^-22 relative.
-template <int NT, bool TIMED = false, bool KLO = true, bool KF32 = false, bool TRAIN = false>
+template <int NT, bool KLO = true, bool KF32 = false, bool TRAIN = false>
 __global__ __launch_bounds__(512, 1) void shared_kv_attention_pp_kernel(
     const float *__restrict__ q, const int64_t *__restrict__ q_start, const int64_t *__restrict__ q_len,
     const _Float16 *__restrict__ kvh, const _Float16 *__restrict__ kvl, const int64_t *__restrict__ kv_start,
     const int64_t *__restrict__ kv_len, float scale, float *__restrict__ out, _Float16 *__restrict__ out_h, _Float16 *__restrict__ out_l,
-    int q_pairs, int n_codes, unsigned long long *__restrict__ dbg = nullptr, float *__restrict__ lse = nullptr, unsigned drop_thresh = 0,
+    int q_pairs, int n_codes, float *__restrict__ lse = nullptr, unsigned drop_thresh = 0,
     unsigned seed = 0, float keep_scale = 1.f)
 {
     using S = AttPP<NT>;
@@ -218,8 +216,6 @@ __global__ __launch_bounds__(512, 1) void shared_kv_attention_pp_kernel(
 
 #define PP_MFMA16(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, x, y, z)
 #define PP_MFMA32(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, x, y, z)
-    unsigned long long t_s = 0, t_x = 0, t_v = 0, t_w = 0, t_0 = 0;
-    if (TIMED) t_0 = __builtin_amdgcn_s_memtime();
     auto phase_s = [&](int c) __attribute__((always_inline)) {
         const unsigned cb = (unsigned)((c & 1) * CHUNKB);
         // ---- S: partial scores of the group's 32 rows x 16 keys over this wave's columns: NT k steps x 2 tiles x 3 passes
@@ -399,45 +395,34 @@ __global__ __launch_bounds__(512, 1) void shared_kv_attention_pp_kernel(
     auto refill = [&](int cp) __attribute__((always_inline)) {
         if (cp >= 1 && cp + 1 < nchunk) stage(cp + 1);
     };
-    auto timed = [&](unsigned long long &acc_t, auto &&fn) __attribute__((always_inline)) {
-        if (TIMED) {
-            const unsigned long long a = __builtin_amdgcn_s_memtime();
-            fn();
-            acc_t += __builtin_amdgcn_s_memtime() - a;
-        } else {
-            fn();
-        }
-    };
+    // (every phase and slot end of the schedule below runs as a closure handed to `slot`: hipcc's code for the NT = 2 instantiations
+    // depends on this level of nesting -- called directly, the ring offset of their chunk loop is computed by other scalar instructions)
+    auto slot = [&](auto &&fn) __attribute__((always_inline)) { fn(); };
     if (grp == 0) {
         for (int c = 0; c < nchunk; ++c) {
-            if (active) timed(t_s, [&]() __attribute__((always_inline)) { phase_s(c); });
-            timed(t_w, [&]() __attribute__((always_inline)) { slot_end(-1); });
+            if (active) slot([&]() __attribute__((always_inline)) { phase_s(c); });
+            slot([&]() __attribute__((always_inline)) { slot_end(-1); });
             refill(c);
-            if (active) timed(t_x, [&]() __attribute__((always_inline)) { phase_x(c); });
-            timed(t_w, [&]() __attribute__((always_inline)) { slot_end(-1); });
-            if (active) timed(t_v, [&]() __attribute__((always_inline)) { phase_v(c); });
-            timed(t_w, [&]() __attribute__((always_inline)) { slot_end(c + 1); });
+            if (active) slot([&]() __attribute__((always_inline)) { phase_x(c); });
+            slot([&]() __attribute__((always_inline)) { slot_end(-1); });
+            if (active) slot([&]() __attribute__((always_inline)) { phase_v(c); });
+            slot([&]() __attribute__((always_inline)) { slot_end(c + 1); });
         }
-        timed(t_w, [&]() __attribute__((always_inline)) { slot_end(-1); });                           // (slot 3 nchunk: g1's last V)
+        slot([&]() __attribute__((always_inline)) { slot_end(-1); });                           // (slot 3 nchunk: g1's last V)
     } else {
-        timed(t_w, [&]() __attribute__((always_inline)) { slot_end(-1); });                           // (slot 0: g0's first S)
+        slot([&]() __attribute__((always_inline)) { slot_end(-1); });                           // (slot 0: g0's first S)
         for (int c = 0; c < nchunk; ++c) {
             refill(c);
-            if (active) timed(t_s, [&]() __attribute__((always_inline)) { phase_s(c); });
-            timed(t_w, [&]() __attribute__((always_inline)) { slot_end(-1); });
-            if (active) timed(t_x, [&]() __attribute__((always_inline)) { phase_x(c); });
-            timed(t_w, [&]() __attribute__((always_inline)) { slot_end(c + 1); });
-            if (active) timed(t_v, [&]() __attribute__((always_inline)) { phase_v(c); });
-            timed(t_w, [&]() __attribute__((always_inline)) { slot_end(-1); });
+            if (active) slot([&]() __attribute__((always_inline)) { phase_s(c); });
+            slot([&]() __attribute__((always_inline)) { slot_end(-1); });
+            if (active) slot([&]() __attribute__((always_inline)) { phase_x(c); });
+            slot([&]() __attribute__((always_inline)) { slot_end(c + 1); });
+            if (active) slot([&]() __attribute__((always_inline)) { phase_v(c); });
+            slot([&]() __attribute__((always_inline)) { slot_end(-1); });
         }
     }
 #undef PP_MFMA16
 #undef PP_MFMA32
-    if (TIMED && dbg && lane == 0) {
-        unsigned long long *o = dbg + ((size_t)blockIdx.x * 8 + (tid >> 6)) * 8;
-        o[0] = t_s; o[1] = t_x; o[2] = t_v; o[3] = t_w; o[4] = __builtin_amdgcn_s_memtime() - t_0; o[5] = (unsigned long long)nchunk; o[6] = active;
-        o[7] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
-    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (gt % TPR == 0) {
         l_s[xrow] = l_run;

@@ -348,8 +348,8 @@ __device__ __forceinline__ void filter_hit(FilterRow<TOPK> &r, float a0, float a
 // runs the hit sequence above.  cb = the lane's first code of this 32-code group.
 // (Round 1 parked hits in LDS and flushed them once per 128 values; with 16 values per scan and row the parking only added
 // LDS round trips -- each behind a drain of the DMA ring, see above.)
-template <int TOPK, bool COUNT = false, bool BIASED = false>
-__device__ __forceinline__ void filter_scan(FilterRow<TOPK> &r, const f32x16 &a, int cb, const char *cbase, unsigned long &multi, unsigned *n_hit = nullptr,
+template <int TOPK, bool BIASED = false>
+__device__ __forceinline__ void filter_scan(FilterRow<TOPK> &r, const f32x16 &a, int cb, const char *cbase, unsigned long &multi,
                                             float cc = 0.f, float bias = 0.f)
 {
     // all four quad maxima and their tests first (the limit does not move inside a tile: filter_hit leaves L alone), then scalar
@@ -362,15 +362,9 @@ __device__ __forceinline__ void filter_scan(FilterRow<TOPK> &r, const f32x16 &a,
 #pragma unroll
     for (int g = 0; g < 4; ++g) h[g] = __builtin_amdgcn_ballot_w64(mx[g] >= r.L);
     if (__builtin_expect((h[0] | h[1] | h[2] | h[3]) != 0, 0)) {
-        unsigned long long t0 = 0;
-        if (COUNT) t0 = __builtin_amdgcn_s_memtime();
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-            if (h[g]) {
-                filter_hit<TOPK, BIASED>(r, a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3], mx[g], cb + 8 * g, cbase, multi, cc, bias);
-                if (COUNT) ++n_hit[0];    // (dev probe: how many of the wave's quad tests run the hit sequence, and for how long)
-            }
-        if (COUNT) n_hit[1] += (unsigned)(__builtin_amdgcn_s_memtime() - t0);
+            if (h[g]) filter_hit<TOPK, BIASED>(r, a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3], mx[g], cb + 8 * g, cbase, multi, cc, bias);
     }
 }
 
@@ -556,11 +550,7 @@ __device__ __forceinline__ void lds_init_wait(f32x16 (&a)[4][2])
 // ring has ONE block-wide barrier per stage, so whatever one wave does beyond its MFMAs in a stage is added to that stage for
 // all eight -- about +990 cycles per scanning stage for ~140 extra instructions, in 16 of 24 stages, against one exposed scan
 // per tile.  What pays instead is making that one scan short (filter_hit above).
-// TIMED (dev probe, tools/r04/filter_probe.py; the product instantiates TIMED = false): every wave accumulates, in shader-clock
-// cycles (s_memtime), how long the five segments of its stage loop take -- MFMA group 1 (+ operand reads), the wait for its own
-// and the block's copies (s_waitcnt, then s_barrier), MFMA group 2 (+ DMA issue), the tile epilogue -- and writes the sums to
-// `dump` (as uint64[blocks][8 waves][8]).
-template <int TOPK, bool DUMP, bool TIMED = false>
+template <int TOPK, bool DUMP>
 __global__ __launch_bounds__(F_THREADS, 2) void filter_f16_kernel(
     const _Float16 *__restrict__ xh, const _Float16 *__restrict__ wh, const float *__restrict__ xsq,
     const float *__restrict__ wsqs, const float *__restrict__ en_max_ptr, long n, int k_codes, int dp, int d,
@@ -821,14 +811,6 @@ __global__ __launch_bounds__(F_THREADS, 2) void filter_f16_kernel(
     // -1.5 % when given to the older half instead; flips around the MFMA groups measured -1 %).
     if (late) __builtin_amdgcn_s_setprio(3);
 
-    unsigned long long tm[6] = {0, 0, 0, 0, 0, 0}, tq = 0;       // TIMED: mfma 1, copy wait, barrier, mfma 2, epilogue, stages
-    auto tick = [&](int k) __attribute__((always_inline)) {
-        if (TIMED) {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            tm[k] += now - tq;
-            tq = now;
-        }
-    };
     // first half of an iteration: MFMA(s, t0) with the operand reads of (s, t1) between them, then the stage barrier
     auto first_half = [&](int s, auto first) __attribute__((always_inline)) {
         if (late && s > 0) stage();         // waves 4-7: stage s+2 (slot s-2, free since the barrier of iteration s-1)
@@ -838,12 +820,9 @@ __global__ __launch_bounds__(F_THREADS, 2) void filter_f16_kernel(
         for (int i = 0; i < F_MT; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, F_NT, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
         // the next step's operands have landed; own part of stage s+1 has landed; then everyone's has
         __builtin_amdgcn_s_waitcnt(LGKM0);
-        tick(0);
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        tick(1);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        tick(2);
     };
     // second half: (DMA of stage s+3,) MFMA(s, t1) with the operand reads of (s+1, t0) between them
     // (past the last stage the reads fetch stale LDS, never used)
@@ -865,23 +844,13 @@ __global__ __launch_bounds__(F_THREADS, 2) void filter_f16_kernel(
         second_half(s);
     };
     int s = 0;
-    if (TIMED) tq = __builtin_amdgcn_s_memtime();
     for (int ct = 0; ct < nct; ++ct) {
         iteration(s, std::true_type{});
-        tick(3);
         ++s;
-        for (int kb = 1; kb < nkb; ++kb, ++s) { iteration(s, std::false_type{}); tick(3); }
+        for (int kb = 1; kb < nkb; ++kb, ++s) iteration(s, std::false_type{});
         tile_epilogue(ct, ct == 0);
-        tick(4);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the clamped tail re-issues may still be in flight
-    if (TIMED) {
-        if (lane == 0 && dump) {
-            unsigned long long *o = reinterpret_cast<unsigned long long *>(dump) + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + wave) * 8;
-            o[0] = tm[0]; o[1] = tm[1]; o[2] = tm[2]; o[3] = tm[3]; o[4] = tm[4]; o[5] = (unsigned long long)nstage; o[6] = (unsigned long long)nct;
-            o[7] = __builtin_amdgcn_s_memrealtime();
-        }
-    }
     if (!DUMP) {
 #pragma unroll
         for (int nn = 0; nn < F_NT; ++nn) {
@@ -930,13 +899,11 @@ constexpr size_t R64_INIT_BYTES = 2 * R64_BM * 4;                 // accumulator
 constexpr size_t R64_SMEM_BYTES = R64_RING_BYTES + R64_THR_BYTES + R64_INIT_BYTES;      // 74 KB -> two blocks per CU
 constexpr int R64_LEARN = 8;                                  // code tiles a block only learns its limits from (and revisits last)
 
-// TIMED (dev probe, tools/r04/filter_probe.py): per-wave s_memtime sums of the loop's segments and the number of hit sequences run,
-// written to `probe` (uint64 [blocks][4 waves][8]).
-template <int TOPK, bool TIMED = false>
+template <int TOPK>
 __global__ __launch_bounds__(R64_THREADS, 2) void filter_rows64_kernel(
     const _Float16 *__restrict__ xh, const _Float16 *__restrict__ wh, const float *__restrict__ xsq,
     const float *__restrict__ wsqs, const float *__restrict__ en_max_ptr, long n, int k_codes, int d,
-    int codes_per_split, int own_total, uint2 *__restrict__ cand, int *__restrict__ cand_cnt, unsigned long long *__restrict__ probe = nullptr)
+    int codes_per_split, int own_total, uint2 *__restrict__ cand, int *__restrict__ cand_cnt)
 {
     static_assert(F_MT == 4 && F_NT == 2, "the wave tile is 128 codes x 64 rows");
     extern __shared__ __attribute__((aligned(16))) char fsm[];
@@ -1081,7 +1048,6 @@ __global__ __launch_bounds__(R64_THREADS, 2) void filter_rows64_kernel(
     };
 
     unsigned long multi = 0;
-    unsigned n_hit[2] = {0, 0};
     float cc = -0x1p-15f;                   // (in a VGPR: the hit sequence's fma takes its one scalar operand for the bias)
     asm volatile("" : "+v"(cc));
     // learning step: the best of each accumulator tile into the lane's list; no appends.  The limits are set by the merges of
@@ -1114,7 +1080,7 @@ __global__ __launch_bounds__(R64_THREADS, 2) void filter_rows64_kernel(
         do {                                                                                                                 \
             const int cb_ = R64_LANE_CB(M, tile);                                                                            \
             _Pragma("unroll") for (int nn = 0; nn < F_NT; ++nn) {                                                            \
-                filter_scan<TOPK, TIMED, true>(row[nn], acc[M][nn], cb_, cbase, multi, n_hit, cc, bias);                      \
+                filter_scan<TOPK, true>(row[nn], acc[M][nn], cb_, cbase, multi, cc, bias);                                    \
                 if (multi) { filter_scan_rest<TOPK, true, true>(row[nn], acc[M][nn], cb_, cbase, cc, bias); multi = 0; }     \
             }                                                                                                                \
             R64_INIT_LDS(M, st + 1);                                                                                         \
@@ -1131,27 +1097,15 @@ __global__ __launch_bounds__(R64_THREADS, 2) void filter_rows64_kernel(
         lds_init_wait(acc);
     };
 
-    unsigned long long tm[5] = {0, 0, 0, 0, 0}, tq = 0;        // TIMED: copy wait, barrier, DMA issue, MFMAs, epilogue
-    auto tick = [&](int k) __attribute__((always_inline)) {
-        if (TIMED) {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            tm[k] += now - tq;
-            tq = now;
-        }
-    };
-    if (TIMED) tq = __builtin_amdgcn_s_memtime();
     // one step up to its epilogue: this wave's share of step t's tile (and wave 0's start values of step t + 1) has landed; then
     // everyone's has, and everyone is past the MFMAs of step t - 1 (the other ring slot) and past the start-value reads of step t
     // (buffer t & 1); the next tile's copy goes out, then the MFMAs.  (Two loops, not one with a branch on the phase: with both
     // epilogues behind one loop head hipcc spilled the x fragments.)
     auto step_head = [&](int t) __attribute__((always_inline)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tick(0);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        tick(1);
         stage_init(t + 2);
-        tick(2);
         mfma_tile(t);                   // (with the copy of step t + 1's tile woven in; past the end: the last tile again, into the slot nobody reads any more)
         // The epilogues read the accumulators with inline-asm v_max3: hipcc's hazard recognizer does not count the wait states an
         // XDL result needs before a VALU read for asm consumers (18 for a 16-pass MFMA), and its scheduler is free to move such a
@@ -1160,25 +1114,17 @@ __global__ __launch_bounds__(R64_THREADS, 2) void filter_rows64_kernel(
         // wait states: nothing reads an accumulator before it, nothing after it is early.
         asm volatile("s_nop 15\n\ts_nop 1"
                      : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[3][0]), "+v"(acc[3][1]));
-        tick(3);
     };
     int t = 0;
     for (; t < W; ++t) {
         step_head(t);
         learn_epilogue(t);
-        tick(4);
     }
     for (; t < nsteps; ++t) {
         step_head(t);
         scan_epilogue(t, __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(t < nct ? 0 : 0x7f800000)));
-        tick(4);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (TIMED && probe && lane == 0) {
-        unsigned long long *o = probe + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8;
-        o[0] = tm[0]; o[1] = tm[1]; o[2] = tm[2]; o[3] = tm[3]; o[4] = tm[4]; o[5] = (unsigned long long)nsteps; o[6] = n_hit[0] | ((unsigned long long)n_hit[1] << 32);
-        o[7] = __builtin_amdgcn_s_memrealtime();
-    }
 #pragma unroll
     for (int nn = 0; nn < F_NT; ++nn) {
         const long xr = row0 + wn * (32 * F_NT) + nn * 32 + li;
@@ -1373,7 +1319,7 @@ __global__ __launch_bounds__(R64N_THREADS, 3) void filter_rows64n_kernel(
 #define R64N_ONE(M)                                                                                                      \
         do {                                                                                                             \
             const int cb_ = R64N_LANE_CB(M, tile);                                                                       \
-            filter_scan<TOPK, false, true>(row, acc[M], cb_, cbase, multi, nullptr, cc, bias);                            \
+            filter_scan<TOPK, true>(row, acc[M], cb_, cbase, multi, cc, bias);                                            \
             if (multi) { filter_scan_rest<TOPK, true, true>(row, acc[M], cb_, cbase, cc, bias); multi = 0; }             \
             R64N_INIT_LDS(M, st + 1);                                                                                    \
         } while (0)
@@ -1809,4 +1755,21 @@ __global__ __launch_bounds__(256) void pad_wsq_kernel(const float *__restrict__ 
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < k_pad) out[i] = i < k ? wsq[i] * -32768.0f : -INFINITY;
+}
+
+// what a finished filter pass left in its workspace (medtok_debug_filter_stats): candidates over all lists, lists at or over capacity,
+// rows handed to the exact kernel, lists in total
+__global__ __launch_bounds__(256) void filter_stats_kernel(const int *__restrict__ cnt, long lists, const int *__restrict__ cnt_tail, long lists_tail,
+                                                           const int *__restrict__ fb_count, unsigned long long *__restrict__ out)
+{
+    unsigned long long cand = 0, full = 0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < lists + lists_tail; i += (long)gridDim.x * 256) {
+        const int c = i < lists ? cnt[i] : cnt_tail[i - lists];
+        cand += (unsigned long long)min(c, F_CAP);
+        full += c >= F_CAP ? 1ull : 0ull;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { cand += __shfl_xor(cand, off, 64); full += __shfl_xor(full, off, 64); }
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&out[0], cand); atomicAdd(&out[1], full); }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { out[2] = (unsigned long long)*fb_count; out[3] = (unsigned long long)(lists + lists_tail); }
 }

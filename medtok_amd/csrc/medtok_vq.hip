@@ -1,16 +1,21 @@
-// medtok_vq.hip -- gfx950 (MI355X / CDNA4) kernels + C ABI of the MedTok VQ hot path.
+// medtok_vq.hip -- gfx950 (MI355X / CDNA4): the C ABI of the MedTok VQ hot path and the host side of its kernels.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared
 // (see medtok_amd/csrc/build.py).  Wave size is 64 everywhere; no other target.
 //
-// Kernels (reference call sites in include/medtok_vq.h):
-//   rownorm_kernel        l2-normalise rows + |row|^2            HBM-bound
-//   search_f32_kernel     N x K nearest-code search, top-k       MFMA-bound (fp32 matrix pipe)
-//   merge_topk_kernel     joins per-code-split partial lists     tiny
-//   soft_assign_kernel    softmax(-d), code mix, STE, sq. error  HBM-bound
-//   sum_scale_kernel      fixed-order fp64 reduction             tiny
-//   ema_*                 histogram, stable radix sort by code, segmented row sum, apply
-//   usage_*               sliding id window + distinct count
+// This file: error and profiler plumbing, launch plans and workspace layouts, launches, and the extern "C" entry points
+// (reference call sites in include/medtok_vq.h).  The kernels live in the headers next to it, one per family:
+//   search_f32.h          row norms, top-k list helpers, exact fp32-MFMA search, merges of partial lists, k > 8 join
+//   filter_f16.h          fp16-MFMA shortlist filter (three kernels), operand images, exact re-score
+//   assign_kernels.h      soft assignment, fixed-order fp64 sum
+//   decode_kernels.h      (token ids, weights) -> embedding, and its backward
+//   embed_kernels.h       code indices -> stored tokens -> embedding
+//   train_kernels.h       sparse backward, normalize backward, InfoNCE
+//   loss_kernels.h        alignment / orthogonality losses
+//   attention_*.h         ragged cross-attention cores (fp32, fp16 x 3, LDS-DMA, two-tile, e_dim = 64) and their backward
+//   pack_kernels.h        the prologue of CrossAttention.pooled
+//   split_gemm.h          split-fp16 and one-pass half-precision dense products, operand images
+//   ema_kernels.h         EMA statistics (histogram, radix sort, segmented sum), EMA apply, usage window
 //
 // Arithmetic order is the one oracle/medtok_oracle.c documents; tests compare bit for bit.
 #include <hip/hip_runtime.h>
@@ -86,12 +91,6 @@ static void prof_push(hipEvent_t a, hipEvent_t b, double flops, int kind)
     g_prof.push_back({a, b, flops, kind});
 }
 
-static int profile_begin_impl(unsigned kinds);
-extern "C" int medtok_profile_begin(void) { return profile_begin_impl(~0u); }
-// ... bracketing only the launches of the kinds in `kinds` (bit k = kind k of medtok_profile_end's arrays): a training step is ~180
-// library launches, and two event records per launch are 0.5 ms of an 11 ms step -- the timed region then carries the events of
-// its dominant kernel only (bench.py), the other kinds come from a pass behind it
-extern "C" int medtok_profile_begin_kinds(unsigned kinds) { return profile_begin_impl(kinds); }
 static int profile_begin_impl(unsigned kinds)
 {
     g_prof_kinds = kinds;
@@ -106,6 +105,11 @@ static int profile_begin_impl(unsigned kinds)
     g_prof_on = true;
     return 0;
 }
+extern "C" int medtok_profile_begin(void) { return profile_begin_impl(~0u); }
+// ... bracketing only the launches of the kinds in `kinds` (bit k = kind k of medtok_profile_end's arrays): a training step is ~180
+// library launches, and two event records per launch are 0.5 ms of an 11 ms step -- the timed region then carries the events of
+// its dominant kernel only (bench.py), the other kinds come from a pass behind it
+extern "C" int medtok_profile_begin_kinds(unsigned kinds) { return profile_begin_impl(kinds); }
 
 extern "C" int medtok_profile_end(double *ms, double *flops, int *launches)
 {
@@ -188,117 +192,8 @@ __device__ __forceinline__ float wave_butterfly_sum(float p)
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 
-// ================================================================= rownorm
-// One wavefront per row.  Lane l owns float4 #(l + 64 t): element i lands in chain
-// (i/4)%64 and each chain accumulates in increasing i -- the oracle's canon_sumsq.
-typedef _Float16 rn_half4 __attribute__((ext_vector_type(4)));
-// xh (optional, NORMALIZE only): the fp16 filter's operand image of the normalised rows, [*, dp] prescaled by 2^8 exactly as
-// to_half_kernel writes it -- the one-call forward saves that kernel's pass over xhat.
-// n_img (with xh): the image has that many rows; those from n on are written as zeros (the filter reads whole row tiles).
-// zero_word: an int the launch clears (the filter's count of rows handed to the exact kernel, when nothing else of the search's
-// preparation runs: a prepared codebook).
-template <bool NORMALIZE>
-__global__ __launch_bounds__(256) void rownorm_kernel(const float *__restrict__ x, long n, int d,
-                                                      float *xhat, float *__restrict__ sqn, _Float16 *__restrict__ xh = nullptr, int dp = 0,
-                                                      long n_img = 0, int *__restrict__ zero_word = nullptr)
-{
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0;
-    if (row >= n) {
-        if (NORMALIZE && xh && row < n_img) {
-            rn_half4 z;
-            z[0] = z[1] = z[2] = z[3] = (_Float16)0.f;
-            for (int i = lane * 4; i < dp; i += 256) *reinterpret_cast<rn_half4 *>(xh + row * dp + i) = z;
-        }
-        return;
-    }
-    const float *src = x + row * d;
-    float *dst = xhat ? xhat + row * d : nullptr;
-    float p = 0.f;
-    if (NORMALIZE) {
-        for (int i = lane * 4; i < d; i += 256) {
-            float4 v = ld4(src + i);
-            p = fmaf(v.x, v.x, p); p = fmaf(v.y, v.y, p); p = fmaf(v.z, v.z, p); p = fmaf(v.w, v.w, p);
-        }
-        const float nrm = sqrtf(wave_butterfly_sum(p));
-        const float den = fmaxf(nrm, 1e-12f);
-        p = 0.f;
-        for (int i = lane * 4; i < d; i += 256) {
-            float4 v = ld4(src + i);
-            v.x = v.x / den; v.y = v.y / den; v.z = v.z / den; v.w = v.w / den;
-            st4(dst + i, v);
-            if (xh) {
-                rn_half4 h;
-                h[0] = (_Float16)(v.x * 256.0f); h[1] = (_Float16)(v.y * 256.0f); h[2] = (_Float16)(v.z * 256.0f); h[3] = (_Float16)(v.w * 256.0f);
-                *reinterpret_cast<rn_half4 *>(xh + row * dp + i) = h;
-            }
-            p = fmaf(v.x, v.x, p); p = fmaf(v.y, v.y, p); p = fmaf(v.z, v.z, p); p = fmaf(v.w, v.w, p);
-        }
-        if (xh) {
-            rn_half4 z;
-            z[0] = z[1] = z[2] = z[3] = (_Float16)0.f;
-            for (int i = d + lane * 4; i < dp; i += 256) *reinterpret_cast<rn_half4 *>(xh + row * dp + i) = z;
-        }
-    } else {
-        for (int i = lane * 4; i < d; i += 256) {
-            float4 v = ld4(src + i);
-            if (dst && dst != src) st4(dst + i, v);
-            p = fmaf(v.x, v.x, p); p = fmaf(v.y, v.y, p); p = fmaf(v.z, v.z, p); p = fmaf(v.w, v.w, p);
-        }
-    }
-    p = wave_butterfly_sum(p);
-    if (sqn && lane == 0) sqn[row] = p;
-}
-
-// Rows of at most 64 floats (the reference's e_dim): rownorm_kernel leaves 48 of a wavefront's 64 lanes without an element.  Here a
-// row has 16 lanes (lane l of its group owns float4 #l, as there), four rows share a wavefront, and the butterfly runs over the
-// offsets 8..1 only -- the offsets 32 and 16 of the one-row kernel add the zeros of idle lanes, so the bits are the same.
-template <bool NORMALIZE>
-__global__ __launch_bounds__(256) void rownorm16_kernel(const float *__restrict__ x, long n, int d,
-                                                        float *xhat, float *__restrict__ sqn, _Float16 *__restrict__ xh = nullptr, int dp = 0,
-                                                        long n_img = 0, int *__restrict__ zero_word = nullptr)
-{
-    const int sub = threadIdx.x & 15;
-    const long row = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0;
-    if (NORMALIZE && xh && row >= n && row < n_img && sub * 4 < dp) {      // image rows past the last input row: zeros
-        rn_half4 z;
-        z[0] = z[1] = z[2] = z[3] = (_Float16)0.f;
-        *reinterpret_cast<rn_half4 *>(xh + row * dp + sub * 4) = z;
-    }
-    const bool live = row < n, mine = live && sub * 4 < d;
-    const long r = live ? row : 0;
-    const float *src = x + r * d + sub * 4;
-    float4 v = mine ? ld4(src) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float p = 0.f;
-    p = fmaf(v.x, v.x, p); p = fmaf(v.y, v.y, p); p = fmaf(v.z, v.z, p); p = fmaf(v.w, v.w, p);
-#pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) p = p + __shfl_xor(p, off, 64);
-    if (NORMALIZE) {
-        const float den = fmaxf(sqrtf(p), 1e-12f);
-        v.x = v.x / den; v.y = v.y / den; v.z = v.z / den; v.w = v.w / den;
-        if (mine) {
-            st4(xhat + r * d + sub * 4, v);
-            if (xh) {
-                rn_half4 h;
-                h[0] = (_Float16)(v.x * 256.0f); h[1] = (_Float16)(v.y * 256.0f); h[2] = (_Float16)(v.z * 256.0f); h[3] = (_Float16)(v.w * 256.0f);
-                *reinterpret_cast<rn_half4 *>(xh + r * dp + sub * 4) = h;
-            }
-        } else if (live && xh && sub * 4 < dp) {
-            rn_half4 z;
-            z[0] = z[1] = z[2] = z[3] = (_Float16)0.f;
-            *reinterpret_cast<rn_half4 *>(xh + r * dp + sub * 4) = z;
-        }
-        p = 0.f;
-        p = fmaf(v.x, v.x, p); p = fmaf(v.y, v.y, p); p = fmaf(v.z, v.z, p); p = fmaf(v.w, v.w, p);
-#pragma unroll
-        for (int off = 8; off >= 1; off >>= 1) p = p + __shfl_xor(p, off, 64);
-    } else if (mine && xhat && xhat != x) {
-        st4(xhat + r * d + sub * 4, v);
-    }
-    if (sqn && live && sub == 0) sqn[row] = p;
-}
+// ================================================================= row norms and the exact fp32 search (kernels: search_f32.h)
+#include "search_f32.h"
 
 // the launch every caller of the row-norm kernels goes through: the 16-lanes-per-row form where a row fits it
 template <bool NORMALIZE>
@@ -322,543 +217,6 @@ extern "C" int medtok_rownorm_f32(const float *x, int64_t n, int d, int normaliz
     if (normalize) launch_rownorm<true>(s, x, (long)n, d, xhat, sqn);
     else launch_rownorm<false>(s, x, (long)n, d, xhat, sqn);
     return check_launch("rownorm");
-}
-
-// single VALU instructions (fminf on MFMA results makes hipcc put a canonicalising v_max in front of each operand)
-__device__ __forceinline__ float vs_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float vs_min3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-
-// ================================================================= top-k list helpers
-// Sorted ascending by (value, index).  A lane meets its codes in increasing index order,
-// so a strict '<' on the value alone implements "ties -> lowest index" during the scan.
-template <int T>
-__device__ __forceinline__ void topk_insert(float (&bv)[T], int (&bi)[T], float v, int c)
-{
-    if (v < bv[T - 1]) {
-#pragma unroll
-        for (int j = T - 1; j >= 1; --j) {
-            const bool lt_prev = v < bv[j - 1];
-            const bool lt = v < bv[j];
-            bv[j] = lt_prev ? bv[j - 1] : (lt ? v : bv[j]);
-            bi[j] = lt_prev ? bi[j - 1] : (lt ? c : bi[j]);
-        }
-        const bool lt0 = v < bv[0];
-        bv[0] = lt0 ? v : bv[0];
-        bi[0] = lt0 ? c : bi[0];
-    }
-}
-
-__device__ __forceinline__ bool lex_lt(float v, int c, float bv, int bc)
-{
-    return v < bv || (v == bv && c < bc);
-}
-
-// A row whose distances are NaN never inserts anything and its list keeps the sentinel index.  Token ids leave the library
-// in range regardless -- slot j falls back to code j (torch.topk / argmin also return valid indices for such rows, so the
-// reference's AMP loop survives an overflowed step; the gathers downstream index the codebook with these ids).
-__device__ __forceinline__ int valid_code(int c, int j, int k_codes) { return (unsigned)c < (unsigned)k_codes ? c : j % k_codes; }
-
-// Same, but for merging lists whose codes are not met in order: compare (value, index).
-template <int T>
-__device__ __forceinline__ void topk_insert_lex(float (&bv)[T], int (&bi)[T], float v, int c)
-{
-    if (lex_lt(v, c, bv[T - 1], bi[T - 1])) {
-#pragma unroll
-        for (int j = T - 1; j >= 1; --j) {
-            const bool lt_prev = lex_lt(v, c, bv[j - 1], bi[j - 1]);
-            const bool lt = lex_lt(v, c, bv[j], bi[j]);
-            const float nv = lt_prev ? bv[j - 1] : (lt ? v : bv[j]);
-            const int ni = lt_prev ? bi[j - 1] : (lt ? c : bi[j]);
-            bv[j] = nv; bi[j] = ni;
-        }
-        const bool lt0 = lex_lt(v, c, bv[0], bi[0]);
-        bv[0] = lt0 ? v : bv[0];
-        bi[0] = lt0 ? c : bi[0];
-    }
-}
-
-// ================================================================= fp32 MFMA search
-// Block = 4 waves, tile = 128 codes x 128 rows, BK = 32.  Codes are the MFMA "A" rows and
-// input rows the "B" columns, so after v_mfma_f32_32x32x2_f32 every lane holds 16 codes of
-// ONE input row: the running top-k is lane-local (no cross-lane traffic until the end).
-// Wave w owns input rows [32w, 32w+32) against all 128 codes (4 accumulator tiles).
-//
-// LDS keeps rows as they are in memory.  Lane (i, h) reads one float4 of each 8-wide k-group at
-// +4h; register c then carries element 8g + 4h + c, and MFMA #c consumes (half 0 -> 8g+c,
-// half 1 -> 8g+4+c).  The accumulation therefore visits each group as 0,4,1,5,2,6,3,7 -- the
-// canonical chain order of the arithmetic contract (oracle/medtok_oracle.c) -- with no data
-// permutation anywhere.  Rows are padded to 36 floats: conflict-free ds_read_b128 (16 lanes x
-// stride 36 dwords hit 16 distinct 4-bank slots) and ds_write_b128.
-constexpr int S_BM = 128, S_BN = 128;
-constexpr int S_BK = 32;                                  // 2 blocks/CU (74 KB LDS); 16 with 3 blocks/CU measured the same
-constexpr int S_LD = S_BK + 4;                            // row stride in floats (36 and 20 are both conflict-free)
-constexpr int S_TILE = S_BM * S_LD;                       // floats per staged operand tile
-constexpr size_t S_LDS_BYTES = (size_t)4 * S_TILE * sizeof(float);   // A[2] + B[2]
-constexpr int S_TPR = S_BK / 8;                           // staging threads per tile row (8 floats each)
-constexpr int S_RPP = 256 / S_TPR;                        // tile rows staged per pass
-constexpr int S_PASSES = S_BM / S_RPP;
-constexpr int S_WPS = S_BK == 32 ? 2 : 3;                 // waves per SIMD the register budget is sized for
-
-// INDIRECT: the block's rows are row_list[row0 .. row0+128) (count read from *row_count on the
-// device) -- the exact fallback for rows the fp16 filter could not shortlist.
-// (the body is a force-inlined function of the block's coordinates: search_f32_kernel takes them from blockIdx, the batched kernel
-// of the small-batch forward -- several searches in one launch -- from its descriptor table)
-// EXCL (the second pass of a search for more than 8 codes per row): codes at or below the row's (distance, index) pair
-// (excl_d[row], excl_i[row]) -- the last entry of the first pass's list -- are skipped, so the pass returns the NEXT best codes in the
-// same total order (distance, then index).
-template <int TOPK, bool FINAL, bool KTAIL, bool INDIRECT, bool EXCL = false>
-__device__ __forceinline__ void search_f32_body(
-    const float *__restrict__ xhat, const float *__restrict__ xsq, const float *__restrict__ what,
-    const float *__restrict__ wsq, long n, int k_codes, int d, int codes_per_split, int topk_out,
-    float *__restrict__ pval, int *__restrict__ pidx, int64_t *__restrict__ out_idx,
-    float *__restrict__ out_dist, const int *__restrict__ row_list, const int *__restrict__ row_count,
-    int list_begin, int list_end, const unsigned block_x, const unsigned block_y,
-    const float *__restrict__ excl_d = nullptr, const int64_t *__restrict__ excl_i = nullptr, int excl_stride = 0)
-{
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    // direct form: this launch covers rows from list_begin on; its partial-result buffers span list_end rows (0 = all n)
-    long row0 = (long)block_x * S_BN + (INDIRECT ? 0 : list_begin);
-    const long part_rows = INDIRECT ? (long)(list_end - list_begin) : (list_end > 0 ? (long)list_end : n);     // row extent of the partial-result buffers
-    if (INDIRECT) {
-        // this launch covers list positions [list_begin, min(*row_count, list_end)); uniform for the whole grid
-        n = min((long)*row_count, (long)list_end);
-        row0 += list_begin;
-        if (row0 >= n) return;
-    }
-    auto actual_row = [&](long pos) -> long {
-        const long c = min(pos, n - 1);
-        return INDIRECT ? (long)row_list[c] : c;
-    };
-    const int split = (int)block_y;
-    const int code_lo = split * codes_per_split;
-    const int code_hi = min(k_codes, code_lo + codes_per_split);
-    const int nct = (code_hi - code_lo + S_BM - 1) / S_BM;
-    const int nkb = (d + S_BK - 1) / S_BK;
-    const int nstage = nct * nkb;
-
-    const int srow = tid / S_TPR, sg = tid % S_TPR;
-    float4 ra[S_PASSES][2], rb[S_PASSES][2];
-    int kvalid = 0;                 // bit0/bit1: which float4 of the staged k-group lies inside D
-    int pct = 0, pkb = 0;           // (code tile, k block) of the next stage to prefetch
-
-    // Loads are unconditional: branching around them makes hipcc drain vmcnt(0) per load.  KTAIL
-    // (D % 32 != 0) clamps the addresses into the row and zeroes the out-of-range float4 when it
-    // is written to LDS (zeros leave the fmaf chain untouched).
-    auto gload = [&]() {
-        const int kofs = pkb * S_BK + sg * 8;
-        int k0 = kofs, k1 = kofs + 4;
-        if (KTAIL) {
-            kvalid = (kofs < d ? 1 : 0) | (kofs + 4 < d ? 2 : 0);
-            k0 = min(k0, d - 4);
-            k1 = min(k1, d - 4);
-        }
-#pragma unroll
-        for (int j = 0; j < S_PASSES; ++j) {
-            const int crow = min(code_lo + pct * S_BM + srow + S_RPP * j, k_codes - 1);
-            const float *p = what + (long)crow * d;
-            const long xr = actual_row(row0 + srow + S_RPP * j);
-            const float *q = xhat + xr * d;
-            ra[j][0] = ld4(p + k0);
-            ra[j][1] = ld4(p + k1);
-            rb[j][0] = ld4(q + k0);
-            rb[j][1] = ld4(q + k1);
-        }
-        if (++pkb == nkb) { pkb = 0; ++pct; }
-    };
-    auto lstore = [&](int buf) {
-        float *A = smem + buf * S_TILE;
-        float *B = smem + 2 * S_TILE + buf * S_TILE;
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int j = 0; j < S_PASSES; ++j) {
-            float *pa = A + (srow + S_RPP * j) * S_LD + sg * 8;
-            float *pb = B + (srow + S_RPP * j) * S_LD + sg * 8;
-            if (KTAIL) {
-                st4(pa, (kvalid & 1) ? ra[j][0] : z);
-                st4(pa + 4, (kvalid & 2) ? ra[j][1] : z);
-                st4(pb, (kvalid & 1) ? rb[j][0] : z);
-                st4(pb + 4, (kvalid & 2) ? rb[j][1] : z);
-            } else {
-                st4(pa, ra[j][0]);
-                st4(pa + 4, ra[j][1]);
-                st4(pb, rb[j][0]);
-                st4(pb + 4, rb[j][1]);
-            }
-        }
-    };
-
-    float bv[TOPK];
-    int bi[TOPK];
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j) { bv[j] = INFINITY; bi[j] = 0; }
-
-    const long mypos = row0 + wave * 32 + li;
-    const long myrow = actual_row(mypos);
-    const float xn = xsq[myrow];
-    float ex_d = -INFINITY;
-    int ex_i = -1;
-    if (EXCL) { ex_d = excl_d[myrow * excl_stride]; ex_i = (int)excl_i[myrow * excl_stride]; }
-
-    f32x16 acc[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-
-    // ---- epilogue of one code tile: d = (|x|^2 + |e|^2) - 2 x.e for this lane's 64 codes, fold into the list
-    auto tile_epilogue = [&](int ct) __attribute__((always_inline)) {
-        // ---- epilogue: d = (|x|^2 + |e|^2) - 2 x.e for this lane's 64 codes, fold into the list
-        const int cbase = code_lo + ct * S_BM;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            // |e|^2 of this lane's 16 codes of the tile: four consecutive codes per register group, so four 16-byte loads
-            // (+2.3 % at K = 16384, k = 5); a group that straddles K or sits on an unaligned slice takes the scalar form
-            // codes at or beyond the split's end get |e|^2 = +inf, i.e. d = +inf: never inserted, and no range test per value
-            float en[16];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c0 = cbase + 32 * m + 8 * g + 4 * lh;
-                // (argmin, TOPK = 1: the 16 scalar loads measured 4 % faster than the vector form -- its epilogue is nothing else)
-                if (TOPK > 1 && c0 + 3 < code_hi && ((reinterpret_cast<uintptr_t>(wsq + c0) & 15) == 0)) {
-                    const float4 e4 = ld4(wsq + c0);
-                    en[4 * g] = e4.x; en[4 * g + 1] = e4.y; en[4 * g + 2] = e4.z; en[4 * g + 3] = e4.w;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float e = wsq[min(c0 + j, k_codes - 1)];        // (unconditional load: a branch around it drains vmcnt)
-                        en[4 * g + j] = c0 + j < code_hi ? e : INFINITY;
-                    }
-                }
-            }
-            // four codes per test: the smallest of their distances against the list's last entry, ONE wave-uniform branch; a
-            // quad in which some lane has a better code is then folded in value by value, in code order as before
-            // (ties -> lowest index).  (+0.6 % at k = 5; the argmin kernel keeps the per-value form: -0.5 % there.)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float dv[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float sum = xn + en[4 * g + j];
-                    const float two = 2.0f * acc[m][4 * g + j];
-                    dv[j] = sum - two;
-                    acc[m][4 * g + j] = 0.f;
-                    if (EXCL) {
-                        const int c = cbase + 32 * m + j + 8 * g + 4 * lh;
-                        if (dv[j] < ex_d || (dv[j] == ex_d && c <= ex_i)) dv[j] = INFINITY;
-                    }
-                }
-                bool any = true;
-                if (TOPK > 1) {
-                    const float mn = vs_min(vs_min3(dv[0], dv[1], dv[2]), dv[3]);      // (NaN never wins a v_min: a NaN distance is never inserted)
-                    any = __builtin_amdgcn_ballot_w64(mn < bv[TOPK - 1]) != 0;
-                }
-                if (any) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) topk_insert<TOPK>(bv, bi, dv[j], cbase + 32 * m + j + 8 * g + 4 * lh);
-                }
-            }
-        }
-    };
-
-    if constexpr (!KTAIL && !INDIRECT) {
-        // ---- operand staging by LDS-DMA (D % 32 == 0, rows addressed directly).  A stage = 32 floats of 128 code rows and 128 input rows, each row 128 B =
-        // eight 16-byte chunks; wave w copies rows [32w, 32w+32) of both tiles, eight rows per global_load_lds_dwordx4 (lane l:
-        // row l >> 3, chunk slot l & 7), straight from L2 into one of TWO 32 KB buffers -- no staging registers, no ds_write pass,
-        // nothing to wait for before the MFMAs of a stage but the barrier.  The rows are unpadded (the DMA's LDS image is
-        // lane-linear), so chunk c of row r is stored in slot c ^ ((r >> 1) & 7): the 16 lanes a ds_read_b128 services together
-        // then hit 16 distinct 16-byte bank groups (rows of equal parity in such a group differ in bits 1..3 of r).  The swizzle is
-        // applied to the per-lane SOURCE address.  Staging through registers + ds_write (the KTAIL form below, which needs it to
-        // zero the columns past D) measured 130.8 TFLOP/s in the main loop against 152 with the staging removed; this form 143.7
-        // (N = 600k, K = 16 384, D = 768; whole kernel 123.2 -> 137.4 TFLOP/s at k = 5, 126.8 -> 134.9 for the argmin at 100k x 8192).
-        constexpr int ROWB = S_BK * 4, TILEB = S_BM * ROWB;            // 128 B per staged row, 16 KB per tile
-        char *lds = reinterpret_cast<char *>(smem);                      // [2 buffers][A tile | B tile]
-        const int d_r = lane >> 3, d_p = lane & 7;                       // row within the instruction, chunk slot
-        // buffer-addressed DMA (SGPR descriptor + loop-invariant 32-bit lane offset + SGPR stage offset; hipcc drains
-        // vmcnt(0) before every ds_read that follows a global_load_lds, but not after the raw-buffer form).  The descriptors
-        // carry the valid byte range: rows past K or past n read as zeros instead of touching memory (such codes get
-        // |e|^2 = +inf in the epilogue, such rows are never written back).
-        // The code-side descriptor is rebuilt per stage for the stage's code tile (base = the tile's first row, range = its rows
-        // inside K: a handful of SALU operations), so every offset stays far below 2^31 whatever K * D is.
-        const float *abase_p = what + (long)code_lo * d, *bbase_p = xhat + row0 * d;
-        const long rows_left = n - row0;
-        const int b_bytes = (int)(rows_left < S_BN ? rows_left : S_BN) * d * 4;
-        const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void *)bbase_p, 0, b_bytes, 0x00020000);
-        unsigned lane_off[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = wave * 32 + 8 * i + d_r;
-            lane_off[i] = (unsigned)(r * d + 4 * (d_p ^ ((r >> 1) & 7))) * 4u;
-        }
-        const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-        int pct = 0, pkb = 0;
-        // One stage = eight DMA instructions per wave.  Issued as a burst they hold the wave (and, through the CU's one address
-        // path, its neighbours) at the head of the stage; instead the descriptor is prepared once per stage and the eight pieces
-        // go out one per group of four MFMAs of the stage's first two k steps.  Past the last stage the same stage is issued
-        // again into the buffer nobody reads (same bytes, harmless): no branch around a DMA.
-        __amdgpu_buffer_rsrc_t ars = brs;
-        int ub = 0;
-        char *abase = lds, *bbase = lds;
-        auto dma_prepare = [&](int buf) __attribute__((always_inline)) {
-            abase = lds + buf * 2 * TILEB + (wave_s * 32) * ROWB; bbase = abase + TILEB;
-            ub = __builtin_amdgcn_readfirstlane(pkb * S_BK * 4);
-            const int tile_codes = __builtin_amdgcn_readfirstlane(min(S_BM, k_codes - code_lo - pct * S_BM));
-            ars = __builtin_amdgcn_make_buffer_rsrc((void *)(abase_p + (long)__builtin_amdgcn_readfirstlane(pct) * S_BM * d), 0, tile_codes * d * 4, 0x00020000);
-            const bool wrap = pkb + 1 == nkb, more = !(wrap && pct + 1 == nct);
-            pkb = more ? (wrap ? 0 : pkb + 1) : pkb;
-            pct += (more && wrap) ? 1 : 0;
-        };
-        auto dma_piece = [&](int i) __attribute__((always_inline)) {          // i = 0..7: A rows 8 (i/2) .. of the wave's 32, then B rows
-            if (i & 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, (__attribute__((address_space(3))) void *)(bbase + 8 * (i >> 1) * ROWB), 16, (int)lane_off[i >> 1], ub, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(ars, (__attribute__((address_space(3))) void *)(abase + 8 * (i >> 1) * ROWB), 16, (int)lane_off[i >> 1], ub, 0, 0);
-        };
-        // fragment addresses: lane (li, lh) reads chunk 2 kk + lh of row li (+ 32 m) -- slot (2 kk + lh) ^ ((li >> 1) & 7).
-        // The fragment reads are asm: hipcc orders a C++ ds_read behind ALL pending LDS-DMA ("s_waitcnt vmcnt(0)": a DMA is a pending
-        // LDS write that might alias), i.e. it drained the stage just issued -- a round trip to the L2 per stage in front of the
-        // MFMAs.  The reads of step kk + 1 are issued before the MFMAs of step kk (two register sets); lgkmcnt is waited by hand.
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
-        const unsigned lds0 = (unsigned)(size_t)lds;
-        unsigned fragA[S_BK / 8], fragB[S_BK / 8];
-#pragma unroll
-        for (int kk = 0; kk < S_BK / 8; ++kk) {
-            fragA[kk] = lds0 + li * ROWB + ((2 * kk + lh) ^ ((li >> 1) & 7)) * 16;
-            fragB[kk] = fragA[kk] + TILEB + wave * 32 * ROWB;
-        }
-        f32x4 af[2][4], bf[2];
-        auto frag_read = [&](int set, int kk, unsigned bufofs) __attribute__((always_inline)) {
-            asm volatile("ds_read_b128 %0, %5\n\tds_read_b128 %1, %6\n\tds_read_b128 %2, %6 offset:4096\n\t"
-                         "ds_read_b128 %3, %6 offset:8192\n\tds_read_b128 %4, %6 offset:12288"
-                         : "=&v"(bf[set]), "=&v"(af[set][0]), "=&v"(af[set][1]), "=&v"(af[set][2]), "=&v"(af[set][3])
-                         : "v"(fragB[kk] + bufofs), "v"(fragA[kk] + bufofs));
-        };
-        auto frag_wait = [&](int set) __attribute__((always_inline)) {
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bf[set]), "+v"(af[set][0]), "+v"(af[set][1]), "+v"(af[set][2]), "+v"(af[set][3]));
-        };
-        static_assert(32 * ROWB == 4096, "fragment offsets above are written for 128-byte staged rows");
-        dma_prepare(0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) dma_piece(i);
-        int ct = 0, kb = 0;
-        for (int s = 0; s < nstage; ++s) {
-            const unsigned bufofs = (unsigned)(s & 1) * (2 * TILEB);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // own part of stage s has landed
-            __builtin_amdgcn_s_barrier();                               // everyone's has; everyone is done with the other buffer
-            asm volatile("" ::: "memory");
-            frag_read(0, 0, bufofs);
-            dma_prepare((s & 1) ^ 1);
-            frag_wait(0);
-#pragma unroll
-            for (int kk = 0; kk < S_BK / 8; ++kk) {
-                const int cur = kk & 1;
-                if (kk + 1 < S_BK / 8) frag_read(cur ^ 1, kk + 1, bufofs);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][m].x, bf[cur].x, acc[m], 0, 0, 0);
-                if (kk < 2) { dma_piece(4 * kk); asm volatile("" ::: "memory"); }
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][m].y, bf[cur].y, acc[m], 0, 0, 0);
-                if (kk < 2) { dma_piece(4 * kk + 1); asm volatile("" ::: "memory"); }
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][m].z, bf[cur].z, acc[m], 0, 0, 0);
-                if (kk < 2) { dma_piece(4 * kk + 2); asm volatile("" ::: "memory"); }
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][m].w, bf[cur].w, acc[m], 0, 0, 0);
-                if (kk < 2) { dma_piece(4 * kk + 3); asm volatile("" ::: "memory"); }
-                if (kk < 2) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
-                }
-                if (kk + 1 < S_BK / 8) frag_wait(cur ^ 1);
-            }
-            if (++kb == nkb) {
-                tile_epilogue(ct);
-                kb = 0;
-                ++ct;
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-    gload();
-    int ct = 0, kb = 0;
-    for (int s = 0; s < nstage; ++s) {
-        const int buf = s & 1;
-        lstore(buf);
-        __syncthreads();
-        if (s + 1 < nstage) gload();
-        const float *A = smem + buf * S_TILE + li * S_LD + lh * 4;
-        const float *B = smem + 2 * S_TILE + buf * S_TILE + (wave * 32 + li) * S_LD + lh * 4;
-#pragma unroll
-        for (int kk = 0; kk < S_BK / 8; ++kk) {
-            const float4 bf = ld4(B + kk * 8);
-            float4 af[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) af[m] = ld4(A + m * 32 * S_LD + kk * 8);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[m].x, bf.x, acc[m], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[m].y, bf.y, acc[m], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[m].z, bf.z, acc[m], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[m].w, bf.w, acc[m], 0, 0, 0);
-        }
-        if (++kb == nkb) {
-            tile_epilogue(ct);
-            kb = 0;
-            ++ct;
-        }
-    }
-    }
-
-    // ---- join the two half-waves that share an input row (disjoint code sets)
-    float pv[TOPK];
-    int pi[TOPK];
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j) { pv[j] = __shfl_xor(bv[j], 32, 64); pi[j] = __shfl_xor(bi[j], 32, 64); }
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j) topk_insert_lex<TOPK>(bv, bi, pv[j], pi[j]);
-
-    if (lh == 0 && mypos < n) {
-        if (FINAL) {
-#pragma unroll
-            for (int j = 0; j < TOPK; ++j)
-                if (j < topk_out) { out_idx[myrow * topk_out + j] = bi[j]; out_dist[myrow * topk_out + j] = bv[j]; }
-        } else {
-            const long base = ((long)split * part_rows + (INDIRECT ? mypos - list_begin : myrow - list_begin)) * TOPK;
-#pragma unroll
-            for (int j = 0; j < TOPK; ++j) { pval[base + j] = bv[j]; pidx[base + j] = bi[j]; }
-        }
-    }
-}
-
-template <int TOPK, bool FINAL, bool KTAIL, bool INDIRECT>
-__global__ __launch_bounds__(256, S_WPS) void search_f32_kernel(
-    const float *__restrict__ xhat, const float *__restrict__ xsq, const float *__restrict__ what,
-    const float *__restrict__ wsq, long n, int k_codes, int d, int codes_per_split, int topk_out,
-    float *__restrict__ pval, int *__restrict__ pidx, int64_t *__restrict__ out_idx,
-    float *__restrict__ out_dist, const int *__restrict__ row_list, const int *__restrict__ row_count,
-    int list_begin, int list_end)
-{
-    search_f32_body<TOPK, FINAL, KTAIL, INDIRECT>(xhat, xsq, what, wsq, n, k_codes, d, codes_per_split, topk_out, pval, pidx, out_idx, out_dist,
-                                                  row_list, row_count, list_begin, list_end, blockIdx.x, blockIdx.y);
-}
-
-template <int TOPK, bool FINAL, bool KTAIL>
-__global__ __launch_bounds__(256, S_WPS) void search_f32_excl_kernel(
-    const float *__restrict__ xhat, const float *__restrict__ xsq, const float *__restrict__ what,
-    const float *__restrict__ wsq, long n, int k_codes, int d, int codes_per_split, int topk_out,
-    float *__restrict__ pval, int *__restrict__ pidx, int64_t *__restrict__ out_idx,
-    float *__restrict__ out_dist, int list_begin, int list_end,
-    const float *__restrict__ excl_d, const int64_t *__restrict__ excl_i, int excl_stride)
-{
-    search_f32_body<TOPK, FINAL, KTAIL, false, true>(xhat, xsq, what, wsq, n, k_codes, d, codes_per_split, topk_out, pval, pidx, out_idx, out_dist,
-                                                     (const int *)nullptr, (const int *)nullptr, list_begin, list_end, blockIdx.x, blockIdx.y,
-                                                     excl_d, excl_i, excl_stride);
-}
-
-// ---- several small searches in ONE launch each of three kernels (the B = 256 forward of the reference's default configuration runs
-// its specific and shared searches as four calls of four launches each: 16 launches of 4-30 us for 2 GFLOP; batched: 3 launches).
-// Same kernels' bodies, same arithmetic, same bits; a descriptor per search, selected by blockIdx.z.
-constexpr int MS_MAX = MEDTOK_MULTI_SEARCH_MAX;   // shared (merged) + text + graph + the two aug views
-struct MultiSearchOne {
-    const float *x;                             // [n, d] rows to quantise
-    const float *what, *wsq;                    // the normalised codebook region [k_codes, d] and its squared norms
-    float *xhat, *xsq;                          // out: F.normalize(x) [n, d], its squared norms [n] (scratch)
-    float *pval; int *pidx;                     // scratch: per-split lists [splits][n][TOPK]
-    int64_t *idx; float *dist, *w, *zq;         // out: [n, topk] ids / distances / weights; [n, d] rows with a row stride
-    float *row_sqerr;                           // out (may be NULL): [n] squared error of the soft assignment per row (training losses)
-    long n, zq_stride, x_stride;                // (x rows may be a column block of a wider matrix)
-    int k_codes, codes_per_split, splits, row_tiles;
-};
-// block_base: the searches' (row tile, code split) blocks in ONE dimension, search after search (block_base[i] = first block of
-// search i, block_base[count] = all).  The search kernel's grid holds exactly the blocks that have work: a 3-D grid of
-// max_tiles x max_splits x count launched 996 blocks for the 444 of a B = 256 forward, and -- blocks going to the 8 XCDs by id --
-// the active ones of the two short searches all landed on XCDs 0, 1, 4, 5: 70 blocks for 64 slots there, a second generation of a few
-// blocks, twice the kernel time (round 6: rocprofv3 counters, profiles/r06_pmc_small_search_*.txt).
-struct MultiSearchArgs { MultiSearchOne s[MS_MAX]; int block_base[MS_MAX + 1]; int count, d, topk; };
-
-__global__ __launch_bounds__(256) void rownorm_multi_kernel(MultiSearchArgs a)
-{
-    const MultiSearchOne &m = a.s[blockIdx.y];
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= m.n) return;
-    const int d = a.d;
-    const float *src = m.x + row * m.x_stride;
-    float *dst = m.xhat + row * d;
-    // (rownorm_kernel<true>, statement for statement: the same bits)
-    float p = 0.f;
-    for (int i = lane * 4; i < d; i += 256) {
-        float4 v = ld4(src + i);
-        p = fmaf(v.x, v.x, p); p = fmaf(v.y, v.y, p); p = fmaf(v.z, v.z, p); p = fmaf(v.w, v.w, p);
-    }
-    const float nrm = sqrtf(wave_butterfly_sum(p));
-    const float den = fmaxf(nrm, 1e-12f);
-    p = 0.f;
-    for (int i = lane * 4; i < d; i += 256) {
-        float4 v = ld4(src + i);
-        v.x = v.x / den; v.y = v.y / den; v.z = v.z / den; v.w = v.w / den;
-        st4(dst + i, v);
-        p = fmaf(v.x, v.x, p); p = fmaf(v.y, v.y, p); p = fmaf(v.z, v.z, p); p = fmaf(v.w, v.w, p);
-    }
-    p = wave_butterfly_sum(p);
-    if (lane == 0) m.xsq[row] = p;
-}
-
-template <int TOPK, bool KTAIL>
-__global__ __launch_bounds__(256, S_WPS) void search_f32_multi_kernel(MultiSearchArgs a)
-{
-    int z = 0;
-#pragma unroll
-    for (int i = 1; i < MS_MAX; ++i) z += (i < a.count && (int)blockIdx.x >= a.block_base[i]) ? 1 : 0;
-    const MultiSearchOne &m = a.s[z];
-    const unsigned local = blockIdx.x - (unsigned)a.block_base[z];
-    const unsigned bx = local % (unsigned)m.row_tiles, by = local / (unsigned)m.row_tiles;
-    search_f32_body<TOPK, false, KTAIL, false>(m.xhat, m.xsq, m.what, m.wsq, m.n, m.k_codes, a.d, m.codes_per_split, a.topk, m.pval, m.pidx,
-                                               (int64_t *)nullptr, (float *)nullptr, (const int *)nullptr, (const int *)nullptr, 0, 0,
-                                               bx, by);
-}
-
-// Joins the per-split candidate lists of one row: 8 lanes per row, each folds every 8th split, then three shuffle rounds.
-// (d, index) is a total order, so the result does not depend on who inserts what when.  (A thread per row walked
-// up to 64 splits x k entries serially: 90 us for a 256-row batch.)
-// LPR lanes per row: 8, or a whole wave (64) for small batches with many splits (256 rows x 128 splits: 28 -> ~12 us).
-template <int TOPK, int LPR = 8>
-__global__ __launch_bounds__(256) void merge_topk_kernel(const float *__restrict__ pval, const int *__restrict__ pidx,
-                                                         long n, int splits, int topk_out,
-                                                         int64_t *__restrict__ out_idx, float *__restrict__ out_dist,
-                                                         const int *__restrict__ row_list, const int *__restrict__ row_count, int k_codes)
-{
-    // with a row list: partial lists are indexed by list position (extent n), results go to row_list[position]
-    constexpr int RPB = 256 / LPR;                       // rows per block
-    const int l8 = threadIdx.x & (LPR - 1);
-    const long pos = (long)blockIdx.x * RPB + (threadIdx.x / LPR);
-    const long limit = row_list ? min(n, (long)*row_count) : n;
-    if ((long)blockIdx.x * RPB >= limit) return;         // (block-uniform: the redo of the rows the filter gave up on normally has none)
-    const long row = min(pos, n - 1);                    // lanes past the end keep shuffling with their group, write nothing
-    float bv[TOPK];
-    int bi[TOPK];
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j) { bv[j] = INFINITY; bi[j] = 0x7fffffff; }
-    for (int s = l8; s < splits; s += LPR) {
-        const long base = ((long)s * n + row) * TOPK;
-#pragma unroll
-        for (int j = 0; j < TOPK; ++j) topk_insert_lex<TOPK>(bv, bi, pval[base + j], pidx[base + j]);
-    }
-#pragma unroll
-    for (int off = LPR / 2; off >= 1; off >>= 1) {
-        float pv[TOPK];
-        int pi[TOPK];
-#pragma unroll
-        for (int j = 0; j < TOPK; ++j) { pv[j] = __shfl_xor(bv[j], off, LPR); pi[j] = __shfl_xor(bi[j], off, LPR); }
-#pragma unroll
-        for (int j = 0; j < TOPK; ++j) topk_insert_lex<TOPK>(bv, bi, pv[j], pi[j]);
-    }
-    if (l8 != 0 || pos >= limit) return;
-    const long orow = row_list ? (long)row_list[pos] : row;
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j)
-        if (j < topk_out) { out_idx[orow * topk_out + j] = valid_code(bi[j], j, k_codes); out_dist[orow * topk_out + j] = bv[j]; }
 }
 
 #include "filter_f16.h"
@@ -899,6 +257,22 @@ static DevInfo dev_info()
     return {cus, cus == 256};
 }
 
+// list length the search kernels are instantiated with for a request of topk <= 8 codes per row
+static inline int list_slots(int topk) { return topk == 1 ? 1 : (topk <= 5 ? 5 : 8); }
+
+// (list length, ragged depth) -> compile-time constants: fn(std::integral_constant<int, T>, std::bool_constant<KTAIL>), T = 1, 5
+// or 8, KTAIL = D % 32 != 0.  Every launch of a kernel that is instantiated per list length goes through here.
+template <typename F>
+static int dispatch_lists(int tslots, bool ragged, F &&fn)
+{
+    auto by_depth = [&](auto t) { return ragged ? fn(t, std::true_type{}) : fn(t, std::false_type{}); };
+    switch (tslots) {
+    case 1: return by_depth(std::integral_constant<int, 1>{});
+    case 5: return by_depth(std::integral_constant<int, 5>{});
+    default: return by_depth(std::integral_constant<int, 8>{});
+    }
+}
+
 struct SearchPlan {
     int tslots;          // list length the kernels are instantiated with (1, 5 or 8)
     int splits;          // code-range splits (grid.y)
@@ -914,7 +288,7 @@ static SearchPlan plan_search(int64_t n, int64_t k_codes, int topk, const PlanOv
 {
     SearchPlan p;
     const DevInfo di = dev_info();
-    p.tslots = topk == 1 ? 1 : (topk <= 5 ? 5 : 8);
+    p.tslots = list_slots(topk);
     p.row_tiles = (n + S_BN - 1) / S_BN;
     const long code_tiles = (k_codes + S_BM - 1) / S_BM;
     // Blocks all cost the same and run 2-3 per CU, so a launch of B blocks wastes up to one "round" of ~2.3 blocks per CU
@@ -955,6 +329,44 @@ static SearchPlan plan_search(int64_t n, int64_t k_codes, int topk, const PlanOv
     return p;
 }
 
+// The exact path's workspace: the partial lists [splits][rows][tslots] of the launch that splits the code range -- the whole search
+// (rows = n), or the tail launch behind whole rounds of unsplit blocks (rows = those of the last round's row tiles).  A search whose
+// blocks all walk every code writes its final lists and needs none: 256 bytes, so that a caller can always allocate what the query
+// returns.  ws == nullptr: sizes only.
+struct ExactWs { float *pval; int *pidx; long rows; size_t total; };
+static ExactWs exact_ws_layout(void *ws, int64_t n, const SearchPlan &p)
+{
+    ExactWs w = {nullptr, nullptr, 0, 256};
+    if (p.tail_splits == 0 && p.splits == 1) return w;
+    const int splits = p.tail_splits > 0 ? p.tail_splits : p.splits;
+    w.rows = p.tail_splits > 0 ? (long)(n - p.main_tiles * S_BN) : (long)n;
+    const size_t vbytes = align_up((size_t)splits * w.rows * p.tslots * sizeof(float), 256);
+    const size_t ibytes = align_up((size_t)splits * w.rows * p.tslots * sizeof(int), 256);
+    if (ws) { w.pval = (float *)ws; w.pidx = (int *)((char *)ws + vbytes); }
+    w.total = vbytes + ibytes;
+    return w;
+}
+
+// ---- more than 8 codes per row (k = 9 .. MEDTOK_MAX_TOPK; the reference takes any k, vector_quantization_soft_one_new.py:91,157,203):
+// the lane-local lists of the kernels hold 8 entries, so the search runs as TWO passes of the exact kernel -- the 8 best codes, then
+// the best k - 8 among the codes behind the row's 8th (distance, index) pair -- and a join.  Same total order (distance, then
+// lowest index) as one list of k: bit-identical to the oracle's top-k.  Always the exact fp32 path (the shortlist kernels keep lists
+// of at most 8).  Workspace: the two passes' lists (ids, then distances), then the workspace both passes use in turn.
+struct WideWs { int64_t *ia, *ib; float *da, *db; void *inner; size_t total; };
+static WideWs wide_ws_layout(void *ws, int64_t n, size_t inner_bytes)
+{
+    WideWs w;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *p = ws ? (char *)ws + off : nullptr; off += align_up(bytes, 256); return (void *)p; };
+    w.ia = (int64_t *)take((size_t)n * WIDE_T * sizeof(int64_t));
+    w.ib = (int64_t *)take((size_t)n * WIDE_T * sizeof(int64_t));
+    w.da = (float *)take((size_t)n * WIDE_T * sizeof(float));
+    w.db = (float *)take((size_t)n * WIDE_T * sizeof(float));
+    w.inner = ws ? (char *)ws + off : nullptr;
+    w.total = off + inner_bytes;
+    return w;
+}
+
 // ---- fp16 filter path: plan + workspace layout
 struct FilterPlan {
     long n_pad, k_pad, row_tiles;
@@ -968,18 +380,21 @@ struct FilterPlan {
     int tail_splits, tail_codes_per_split, own_tail;
 };
 
+// width of the filter's fp16 operand images at depth d.
+// At least TWO 32-deep stages per code tile: the start values of code tile t + 2 are copied (LDS-DMA, wave 0) at the end of tile
+// t's scan and read at the end of tile t + 1's, and what guarantees that they have landed is the counted vmcnt wait of a LATER
+// stage -- with one stage per tile there is none in between (found by tools/fuzz_search.py at D = 4 / 32: one wave's 64 rows
+// wrong in ~1 % of the searches).  D <= 32 is zero-padded to 64 and takes the narrow-row kernel like every D <= 64.
+static inline int filter_image_dp(int d) { return (int)lmax(2 * F_BK, (d + F_BK - 1) / F_BK * F_BK); }
+
 static FilterPlan plan_filter(int64_t n, int64_t k_codes, int d, int topk, const PlanOverride &ov)
 {
     FilterPlan f;
     const DevInfo di = dev_info();
-    f.tslots = topk == 1 ? 1 : (topk <= 5 ? 5 : 8);
+    f.tslots = list_slots(topk);
     f.n_pad = (n + F_BN - 1) / F_BN * F_BN;
     f.k_pad = (k_codes + F_BM - 1) / F_BM * F_BM;
-    // at least TWO 32-deep stages per code tile: the start values of code tile t + 2 are copied (LDS-DMA, wave 0) at the end of tile
-    // t's scan and read at the end of tile t + 1's, and what guarantees that they have landed is the counted vmcnt wait of a LATER
-    // stage -- with one stage per tile there is none in between (found by tools/fuzz_search.py at D = 4 / 32: one wave's 64 rows
-    // wrong in ~1 % of the searches).  D <= 32 is zero-padded to 64 and takes the narrow-row kernel like every D <= 64.
-    f.dp = (int)lmax(2 * F_BK, (d + F_BK - 1) / F_BK * F_BK);
+    f.dp = filter_image_dp(d);
     f.row_tiles = f.n_pad / F_BN;
     const long code_tiles = f.k_pad / F_BM;
     f.rows64 = f.dp == 64 && ov.filter_rows64 != 0;
@@ -1056,6 +471,7 @@ struct FilterWs {
     int *cnt_tail;
     int *cand_cnt, *fb_count, *fb_rows, *fb_pidx;
     float *fb_pval;
+    long n_main, n_tail;     // rows whose candidate lists the main / the tail launch writes
     size_t total;
 };
 
@@ -1077,11 +493,11 @@ static FilterWs filter_ws_layout(void *ws, int64_t n, const FilterPlan &f)
     w.fb_rows = (int *)take((size_t)n * 4);
     w.fb_pval = (float *)take((size_t)FB_SPLITS * FB_ROWS * MEDTOK_MAX_TOPK * 4);
     w.fb_pidx = (int *)take((size_t)FB_SPLITS * FB_ROWS * MEDTOK_MAX_TOPK * 4);
-    const size_t n_main = (size_t)lmin(n, f.main_tiles * f.row_bn), n_tail = (size_t)n - n_main;
-    w.cand_cnt = (int *)take(n_main * f.own_total * 4);
-    w.cand = (uint2 *)take(n_main * f.own_total * F_CAP * 8);
-    w.cnt_tail = (int *)take(n_tail * f.own_tail * 4);
-    w.cand_tail = (uint2 *)take(n_tail * f.own_tail * F_CAP * 8);
+    w.n_main = lmin(n, f.main_tiles * f.row_bn); w.n_tail = (long)n - w.n_main;
+    w.cand_cnt = (int *)take((size_t)w.n_main * f.own_total * 4);
+    w.cand = (uint2 *)take((size_t)w.n_main * f.own_total * F_CAP * 8);
+    w.cnt_tail = (int *)take((size_t)w.n_tail * f.own_tail * 4);
+    w.cand_tail = (uint2 *)take((size_t)w.n_tail * f.own_tail * F_CAP * 8);
     w.dump = nullptr;
     w.total = off;
     return w;
@@ -1109,8 +525,6 @@ static bool filter_eligible(int64_t n, int64_t k_codes, int d, int topk)
     return true;
 }
 
-static size_t wide_head_bytes(int64_t n);
-
 static int resolve_path(int path, int64_t n, int64_t k_codes, int d, int topk)
 {
     path = path_id(path);
@@ -1120,151 +534,135 @@ static int resolve_path(int path, int64_t n, int64_t k_codes, int d, int topk)
     return path;
 }
 
-extern "C" size_t medtok_search_workspace_bytes(int64_t n, int64_t k_codes, int d, int topk, int path)
+// Everything a search call derives from its shape and its `path` argument, derived ONCE: the size queries, the launches and the
+// test hooks all read this struct, so a plan and the workspace laid out for it cannot disagree.  Built for any arguments (the
+// entry points check theirs later, after what they launch first): a shape no search runs on gives the exact path with no workspace.
+struct SearchCall {
+    PlanOverride ov;
+    int requested = MEDTOK_PATH_AUTO;        // the `path` argument's path id, as the caller gave it
+    int path = MEDTOK_PATH_F32_MFMA;         // the path that runs: MEDTOK_PATH_F32_MFMA or MEDTOK_PATH_F16_FILTER
+    int tslots = 0;                          // list length of the kernels' instantiation; 8 for both passes of a search for k > 8
+    bool ragged = false;                     // d % S_BK != 0: the KTAIL instantiations of the exact kernel
+    bool wide = false;                       // k > 8: two exact passes and a join (search_wide)
+    SearchPlan exact = {};                   // path == MEDTOK_PATH_F32_MFMA
+    FilterPlan filter = {};                  // path == MEDTOK_PATH_F16_FILTER
+    size_t ws_bytes = 0;
+};
+
+static SearchCall plan_search_call(int64_t n, int64_t k_codes, int d, int topk, int path)
 {
-    if (n <= 0 || k_codes <= 0 || topk < 1 || topk > MEDTOK_MAX_TOPK) return 0;
-    if (topk > 8)            // two passes of the exact kernel with lists of 8 + the join's buffers
-        return wide_head_bytes(n) + medtok_search_workspace_bytes(n, k_codes, d, 8, (path & ~MEDTOK_PATH_MASK) | MEDTOK_PATH_F32_MFMA);
-    const PlanOverride ov = decode_plan(path);
-    if (resolve_path(path, n, k_codes, d, topk) == MEDTOK_PATH_F16_FILTER)
-        return filter_ws_layout(nullptr, n, plan_filter(n, k_codes, d, topk, ov)).total;
-    SearchPlan p = plan_search(n, k_codes, topk, ov);
-    if (p.tail_splits > 0) {
-        const size_t tail_rows = (size_t)(n - p.main_tiles * S_BN);
-        return align_up((size_t)p.tail_splits * tail_rows * p.tslots * sizeof(float), 256) +
-               align_up((size_t)p.tail_splits * tail_rows * p.tslots * sizeof(int), 256);
+    SearchCall c;
+    c.ov = decode_plan(path);
+    c.requested = path_id(path);
+    c.ragged = d % S_BK != 0;
+    if (n <= 0 || k_codes <= 0 || topk < 1 || topk > MEDTOK_MAX_TOPK) return c;
+    c.path = resolve_path(path, n, k_codes, d, topk);
+    c.wide = topk > 8;
+    if (c.path == MEDTOK_PATH_F16_FILTER) {
+        c.filter = plan_filter(n, k_codes, d, topk, c.ov);
+        c.tslots = c.filter.tslots;
+        c.ws_bytes = filter_ws_layout(nullptr, n, c.filter).total;
+    } else {
+        c.exact = plan_search(n, k_codes, c.wide ? WIDE_T : topk, c.ov);
+        c.tslots = c.exact.tslots;
+        c.ws_bytes = exact_ws_layout(nullptr, n, c.exact).total;
+        if (c.wide) c.ws_bytes = wide_ws_layout(nullptr, n, c.ws_bytes).total;
     }
-    if (p.splits == 1) return 256;
-    return align_up((size_t)p.splits * n * p.tslots * sizeof(float), 256) +
-           align_up((size_t)p.splits * n * p.tslots * sizeof(int), 256);
+    return c;
 }
 
-template <int T, bool KTAIL>
+extern "C" size_t medtok_search_workspace_bytes(int64_t n, int64_t k_codes, int d, int topk, int path)
+{
+    return plan_search_call(n, k_codes, d, topk, path).ws_bytes;
+}
+
+extern "C" int medtok_search_resolved_path(int64_t n, int64_t k_codes, int d, int topk, int path)
+{
+    if (d <= 0) return MEDTOK_PATH_F32_MFMA;
+    return plan_search_call(n, k_codes, d, topk, path).path;
+}
+
+// the second pass of a search for k > 8: skip, per row, the codes at or below the (distance, index) pair at excl_d / excl_i [row * stride]
+struct Exclude { const float *d; const int64_t *i; int stride; };
+
+// The exact search of one plan (lists of T entries): one launch whose blocks walk all codes and write the final lists, or partial
+// lists per code split and their merge, or -- large searches -- whole rounds of the first form and a tail launch of the second.
+// EXCL: the exclusion pass (lists of 8 only).
+template <int T, bool KTAIL, bool EXCL = false>
 static int launch_search(const float *xhat, const float *xsq, int64_t n, const float *what, const float *wsq,
                          int64_t k_codes, int d, int topk, int64_t *idx, float *dist, void *ws, size_t ws_bytes,
-                         const SearchPlan &p, hipStream_t s, const float *excl_d = nullptr, const int64_t *excl_i = nullptr, int excl_stride = 0)
+                         const SearchPlan &p, hipStream_t s, Exclude ex = {nullptr, nullptr, 0})
 {
+    static_assert(!EXCL || T == WIDE_T, "the exclusion pass runs with lists of 8");
     dim3 grid((unsigned)p.row_tiles, (unsigned)p.splits), block(256);
     hipEvent_t pa = prof_wanted(1) ? prof_mark(s) : nullptr;
     const double pflops = 2.0 * (double)n * (double)k_codes * (double)d;
-    // one launch of the exact kernel: FINAL (a block walks all codes and writes the row's list) or partial lists per code split;
-    // with excl_d the second-pass form that skips a row's first-pass codes (lists of 8 only)
-    auto go = [&](bool final_, dim3 g, int cps, float *pv, int *pi, int64_t *oi, float *od, int lb, int le) {
-        if (excl_d) {
-            if constexpr (T == 8) {
-                if (final_) {
-                    (void)set_lds_once<search_f32_excl_kernel<8, true, KTAIL>>(S_LDS_BYTES);
-                    hipLaunchKernelGGL((search_f32_excl_kernel<8, true, KTAIL>), g, block, S_LDS_BYTES, s, xhat, xsq, what, wsq, (long)n, (int)k_codes, d, cps, topk,
-                                       pv, pi, oi, od, lb, le, excl_d, excl_i, excl_stride);
-                } else {
-                    (void)set_lds_once<search_f32_excl_kernel<8, false, KTAIL>>(S_LDS_BYTES);
-                    hipLaunchKernelGGL((search_f32_excl_kernel<8, false, KTAIL>), g, block, S_LDS_BYTES, s, xhat, xsq, what, wsq, (long)n, (int)k_codes, d, cps, topk,
-                                       pv, pi, oi, od, lb, le, excl_d, excl_i, excl_stride);
-                }
-            }
-            return;
-        }
-        if (final_) {
-            (void)set_lds_once<search_f32_kernel<T, true, KTAIL, false>>(S_LDS_BYTES);
-            hipLaunchKernelGGL((search_f32_kernel<T, true, KTAIL, false>), g, block, S_LDS_BYTES, s, xhat, xsq, what, wsq, (long)n, (int)k_codes, d, cps, topk,
-                               pv, pi, oi, od, (const int *)nullptr, (const int *)nullptr, lb, le);
+    // one launch of the exact kernel: FINAL (a block walks all codes and writes the row's list) or partial lists per code split
+    auto go = [&](auto final_, dim3 g, int cps, float *pv, int *pi, int64_t *oi, float *od, int lb, int le) {
+        constexpr bool FINAL = decltype(final_)::value;
+        if constexpr (EXCL) {
+            (void)set_lds_once<search_f32_excl_kernel<T, FINAL, KTAIL>>(S_LDS_BYTES);
+            hipLaunchKernelGGL((search_f32_excl_kernel<T, FINAL, KTAIL>), g, block, S_LDS_BYTES, s, xhat, xsq, what, wsq, (long)n, (int)k_codes, d, cps, topk,
+                               pv, pi, oi, od, lb, le, ex.d, ex.i, ex.stride);
         } else {
-            (void)set_lds_once<search_f32_kernel<T, false, KTAIL, false>>(S_LDS_BYTES);
-            hipLaunchKernelGGL((search_f32_kernel<T, false, KTAIL, false>), g, block, S_LDS_BYTES, s, xhat, xsq, what, wsq, (long)n, (int)k_codes, d, cps, topk,
+            (void)set_lds_once<search_f32_kernel<T, FINAL, KTAIL, false>>(S_LDS_BYTES);
+            hipLaunchKernelGGL((search_f32_kernel<T, FINAL, KTAIL, false>), g, block, S_LDS_BYTES, s, xhat, xsq, what, wsq, (long)n, (int)k_codes, d, cps, topk,
                                pv, pi, oi, od, (const int *)nullptr, (const int *)nullptr, lb, le);
         }
     };
-    if (excl_d && T != 8) return fail("search: the exclusion pass runs with lists of 8");
+    const ExactWs w = exact_ws_layout(ws, n, p);
+    if (p.tail_splits == 0 && p.splits == 1) {
+        go(std::true_type{}, grid, p.codes_per_split, (float *)nullptr, (int *)nullptr, idx, dist, 0, 0);
+        if (pa) prof_push(pa, prof_mark(s), pflops, 1);
+        return check_launch("search_f32");
+    }
+    if (!ws || ws_bytes < w.total) return fail("search: workspace too small (%zu < %zu)", ws_bytes, w.total);
     if (p.tail_splits > 0) {
         // whole rounds of unsplit blocks, then the last round's row tiles with their own code splits + merge
-        const long tail_start = p.main_tiles * S_BN, tail_rows = n - tail_start;
-        const size_t vb = align_up((size_t)p.tail_splits * tail_rows * T * sizeof(float), 256);
-        const size_t ib = align_up((size_t)p.tail_splits * tail_rows * T * sizeof(int), 256);
-        if (!ws || ws_bytes < vb + ib) return fail("search: workspace too small (%zu < %zu)", ws_bytes, vb + ib);
-        float *pval = (float *)ws;
-        int *pidx = (int *)((char *)ws + vb);
-        go(true, dim3((unsigned)p.main_tiles, 1), p.codes_per_split, (float *)nullptr, (int *)nullptr, idx, dist, 0, 0);
-        go(false, dim3((unsigned)(p.row_tiles - p.main_tiles), (unsigned)p.tail_splits), p.tail_codes_per_split, pval, pidx, (int64_t *)nullptr, (float *)nullptr,
-           (int)tail_start, (int)tail_rows);
+        const long tail_start = p.main_tiles * S_BN;
+        go(std::true_type{}, dim3((unsigned)p.main_tiles, 1), p.codes_per_split, (float *)nullptr, (int *)nullptr, idx, dist, 0, 0);
+        go(std::false_type{}, dim3((unsigned)(p.row_tiles - p.main_tiles), (unsigned)p.tail_splits), p.tail_codes_per_split, w.pval, w.pidx, (int64_t *)nullptr,
+           (float *)nullptr, (int)tail_start, (int)w.rows);
         if (pa) prof_push(pa, prof_mark(s), pflops, 1);
         if (check_launch("search_f32(main + tail)")) return 1;
-        hipLaunchKernelGGL((merge_topk_kernel<T>), dim3((unsigned)((tail_rows + 31) / 32)), dim3(256), 0, s, pval, pidx, tail_rows,
+        hipLaunchKernelGGL((merge_topk_kernel<T>), dim3((unsigned)((w.rows + 31) / 32)), dim3(256), 0, s, w.pval, w.pidx, w.rows,
                            p.tail_splits, topk, idx + tail_start * topk, dist + tail_start * topk, (const int *)nullptr, (const int *)nullptr,
                            (int)k_codes);
         return check_launch("merge_topk(tail)");
     }
-    if (p.splits == 1) {
-        go(true, grid, p.codes_per_split, (float *)nullptr, (int *)nullptr, idx, dist, 0, 0);
-        if (pa) prof_push(pa, prof_mark(s), pflops, 1);
-        return check_launch("search_f32");
-    }
-    const size_t vbytes = align_up((size_t)p.splits * n * T * sizeof(float), 256);
-    const size_t ibytes = align_up((size_t)p.splits * n * T * sizeof(int), 256);
-    if (!ws || ws_bytes < vbytes + ibytes) return fail("search: workspace too small (%zu < %zu)", ws_bytes, vbytes + ibytes);
-    float *pval = (float *)ws;
-    int *pidx = (int *)((char *)ws + vbytes);
-    go(false, grid, p.codes_per_split, pval, pidx, (int64_t *)nullptr, (float *)nullptr, 0, 0);
+    go(std::false_type{}, grid, p.codes_per_split, w.pval, w.pidx, (int64_t *)nullptr, (float *)nullptr, 0, 0);
     if (pa) prof_push(pa, prof_mark(s), pflops, 1);
     if (check_launch("search_f32(split)")) return 1;
     if (p.splits >= 64 && n <= 8192)     // few rows, many lists each: a wave per row
-        hipLaunchKernelGGL((merge_topk_kernel<T, 64>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, pval, pidx, (long)n,
+        hipLaunchKernelGGL((merge_topk_kernel<T, 64>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, w.pval, w.pidx, (long)n,
                            p.splits, topk, idx, dist, (const int *)nullptr, (const int *)nullptr, (int)k_codes);
     else
-        hipLaunchKernelGGL((merge_topk_kernel<T>), dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s, pval, pidx, (long)n,
+        hipLaunchKernelGGL((merge_topk_kernel<T>), dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s, w.pval, w.pidx, (long)n,
                            p.splits, topk, idx, dist, (const int *)nullptr, (const int *)nullptr, (int)k_codes);
     return check_launch("merge_topk");
 }
 
-template <int T>
-static int launch_search_t(const float *xhat, const float *xsq, int64_t n, const float *what, const float *wsq,
-                           int64_t k_codes, int d, int topk, int64_t *idx, float *dist, void *ws, size_t ws_bytes,
-                           const SearchPlan &p, hipStream_t s, const float *excl_d = nullptr, const int64_t *excl_i = nullptr, int excl_stride = 0)
+// the two passes and the join of a search for more than 8 codes per row (wide_ws_layout)
+static int search_wide(const SearchCall &c, const float *xhat, const float *xsq, int64_t n, const float *what, const float *wsq, int64_t k_codes, int d,
+                       int topk, int64_t *idx, float *dist, void *ws, size_t ws_bytes, hipStream_t s)
 {
-    if (d % S_BK) return launch_search<T, true>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, p, s, excl_d, excl_i, excl_stride);
-    return launch_search<T, false>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, p, s, excl_d, excl_i, excl_stride);
-}
-
-// ---- more than 8 codes per row (k = 9 .. MEDTOK_MAX_TOPK; the reference takes any k, vector_quantization_soft_one_new.py:91,157,203):
-// the lane-local lists of the kernels hold 8 entries, so the search runs as TWO passes of the exact kernel -- the 8 best codes, then
-// the best k - 8 among the codes behind the row's 8th (distance, index) pair -- and a join.  Same total order (distance, then
-// lowest index) as one list of k: bit-identical to the oracle's top-k.  Always the exact fp32 path (the shortlist kernels keep lists
-// of at most 8).
-constexpr int WIDE_T = 8;
-static size_t wide_head_bytes(int64_t n)
-{
-    return 2 * align_up((size_t)n * WIDE_T * sizeof(int64_t), 256) + 2 * align_up((size_t)n * WIDE_T * sizeof(float), 256);
-}
-
-__global__ __launch_bounds__(256) void join_lists_kernel(const int64_t *__restrict__ ia, const float *__restrict__ da, const int64_t *__restrict__ ib,
-                                                         const float *__restrict__ db, long n, int kb, int64_t *__restrict__ idx, float *__restrict__ dist)
-{
-    const int k = WIDE_T + kb;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n * k; i += (long)gridDim.x * 256) {
-        const long r = i / k;
-        const int j = (int)(i - r * k);
-        idx[i] = j < WIDE_T ? ia[r * WIDE_T + j] : ib[r * kb + (j - WIDE_T)];
-        dist[i] = j < WIDE_T ? da[r * WIDE_T + j] : db[r * kb + (j - WIDE_T)];
-    }
-}
-
-static int search_wide(const float *xhat, const float *xsq, int64_t n, const float *what, const float *wsq, int64_t k_codes, int d, int topk,
-                       int64_t *idx, float *dist, void *ws, size_t ws_bytes, int path, hipStream_t s)
-{
-    const PlanOverride ov = decode_plan(path);
-    const SearchPlan p = plan_search(n, k_codes, WIDE_T, ov);
-    const size_t head = wide_head_bytes(n);
-    if (!ws || ws_bytes < head) return fail("search(k > 8): workspace too small (%zu < %zu)", ws_bytes, head);
-    char *base = (char *)ws;
-    int64_t *ia = (int64_t *)base;
-    int64_t *ib = (int64_t *)(base + align_up((size_t)n * WIDE_T * sizeof(int64_t), 256));
-    float *da = (float *)(base + 2 * align_up((size_t)n * WIDE_T * sizeof(int64_t), 256));
-    float *db = (float *)((char *)da + align_up((size_t)n * WIDE_T * sizeof(float), 256));
-    void *inner = base + head;
-    const size_t inner_bytes = ws_bytes - head;
-    if (launch_search_t<WIDE_T>(xhat, xsq, n, what, wsq, k_codes, d, WIDE_T, ia, da, inner, inner_bytes, p, s)) return 1;
+    const size_t inner_bytes = exact_ws_layout(nullptr, n, c.exact).total;
+    const WideWs w = wide_ws_layout(ws, n, inner_bytes);
+    if (!ws || ws_bytes < w.total) return fail("search(k > 8): workspace too small (%zu < %zu)", ws_bytes, w.total);
     const int kb = topk - WIDE_T;
-    if (launch_search_t<WIDE_T>(xhat, xsq, n, what, wsq, k_codes, d, kb, ib, db, inner, inner_bytes, p, s, da + (WIDE_T - 1), ia + (WIDE_T - 1), WIDE_T)) return 1;
-    hipLaunchKernelGGL(join_lists_kernel, dim3((unsigned)lmin(4096, (n * topk + 255) / 256)), dim3(256), 0, s, ia, da, ib, db, (long)n, kb, idx, dist);
+    const int rc = dispatch_lists(c.tslots, c.ragged, [&](auto t, auto ktail) {
+        constexpr int T = decltype(t)::value;
+        constexpr bool KTAIL = decltype(ktail)::value;
+        if constexpr (T == WIDE_T) {
+            if (launch_search<T, KTAIL>(xhat, xsq, n, what, wsq, k_codes, d, WIDE_T, w.ia, w.da, w.inner, inner_bytes, c.exact, s)) return 1;
+            return launch_search<T, KTAIL, true>(xhat, xsq, n, what, wsq, k_codes, d, kb, w.ib, w.db, w.inner, inner_bytes, c.exact, s,
+                                                 Exclude{w.da + (WIDE_T - 1), w.ia + (WIDE_T - 1), WIDE_T});
+        } else {
+            return fail("search: the exclusion pass runs with lists of 8");
+        }
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(join_lists_kernel, dim3((unsigned)lmin(4096, (n * topk + 255) / 256)), dim3(256), 0, s, w.ia, w.da, w.ib, w.db, (long)n, kb, idx, dist);
     return check_launch("join_lists");
 }
 
@@ -1278,9 +676,8 @@ struct FuseAssign { const float *xref; float *w; float *zq; long zq_stride; bool
 template <int T, bool KTAIL>
 static int launch_filter(const float *xhat, const float *xsq, int64_t n, const float *what, const float *wsq,
                          int64_t k_codes, int d, int topk, int64_t *idx, float *dist, void *ws, size_t ws_bytes,
-                         hipStream_t s, FuseAssign *fuse, const PlanOverride &ov)
+                         hipStream_t s, FuseAssign *fuse, const FilterPlan &f)
 {
-    const FilterPlan f = plan_filter(n, k_codes, d, topk, ov);
     const FilterWs w = filter_ws_layout(ws, n, f);
     if (!ws || ws_bytes < w.total) return fail("search(filter): workspace too small (%zu < %zu)", ws_bytes, w.total);
     const bool prep = fuse && fuse->p_wh && fuse->p_wsqp && fuse->p_en_max;
@@ -1355,91 +752,34 @@ static int launch_filter(const float *xhat, const float *xsq, int64_t n, const f
     return check_launch("search_f32(fallback)");
 }
 
-template <int T>
-static int launch_filter_t(const float *xhat, const float *xsq, int64_t n, const float *what, const float *wsq,
-                           int64_t k_codes, int d, int topk, int64_t *idx, float *dist, void *ws, size_t ws_bytes, hipStream_t s,
-                           FuseAssign *fuse, const PlanOverride &ov)
-{
-    if (d % S_BK) return launch_filter<T, true>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, s, fuse, ov);
-    return launch_filter<T, false>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, s, fuse, ov);
-}
-
+// The search of a planned call (c = plan_search_call of the same shape and `path`).
 // `fuse` (internal callers only): when the filter path runs, its re-score kernel also does the soft assignment described there
-static int search_impl(const float *xhat, const float *xsq, int64_t n, const float *what,
+static int search_impl(const SearchCall &c, const float *xhat, const float *xsq, int64_t n, const float *what,
                        const float *wsq, int64_t k_codes, int d, int topk, int64_t *idx, float *dist,
-                       void *ws, size_t ws_bytes, int path, void *stream, FuseAssign *fuse)
+                       void *ws, size_t ws_bytes, void *stream, FuseAssign *fuse)
 {
     if (n < 0 || k_codes <= 0 || d <= 0 || (d & 3)) return fail("search: bad shape n=%ld K=%ld d=%d (d %% 4 == 0)", (long)n, (long)k_codes, d);
     if (topk < 1 || topk > MEDTOK_MAX_TOPK || topk > k_codes) return fail("search: topk=%d unsupported (1..%d, <= K)", topk, MEDTOK_MAX_TOPK);
     if (k_codes >= (1ll << 31)) return fail("search: K too large");
-    if (path_id(path) != MEDTOK_PATH_AUTO && path_id(path) != MEDTOK_PATH_F32_MFMA && path_id(path) != MEDTOK_PATH_F16_FILTER) return fail("search: unknown path %d", path_id(path));
-    const PlanOverride ov = decode_plan(path);
+    if (c.requested != MEDTOK_PATH_AUTO && c.requested != MEDTOK_PATH_F32_MFMA && c.requested != MEDTOK_PATH_F16_FILTER) return fail("search: unknown path %d", c.requested);
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (topk > 8) return search_wide(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, path, s);
-    const int tslots = topk == 1 ? 1 : (topk <= 5 ? 5 : 8);
-    if (resolve_path(path, n, k_codes, d, topk) == MEDTOK_PATH_F16_FILTER) {
-        if (n >= (1ll << 31)) return fail("search(filter): n too large");
-        switch (tslots) {
-        case 1: return launch_filter_t<1>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, s, fuse, ov);
-        case 5: return launch_filter_t<5>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, s, fuse, ov);
-        default: return launch_filter_t<8>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, s, fuse, ov);
-        }
-    }
-    const SearchPlan p = plan_search(n, k_codes, topk, ov);
-    switch (tslots) {
-    case 1: return launch_search_t<1>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, p, s);
-    case 5: return launch_search_t<5>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, p, s);
-    default: return launch_search_t<8>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, p, s);
-    }
+    if (c.wide) return search_wide(c, xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, s);
+    if (c.path == MEDTOK_PATH_F16_FILTER && n >= (1ll << 31)) return fail("search(filter): n too large");
+    return dispatch_lists(c.tslots, c.ragged, [&](auto t, auto ktail) {
+        constexpr int T = decltype(t)::value;
+        constexpr bool KTAIL = decltype(ktail)::value;
+        if (c.path == MEDTOK_PATH_F16_FILTER)
+            return launch_filter<T, KTAIL>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, s, fuse, c.filter);
+        return launch_search<T, KTAIL>(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, c.exact, s);
+    });
 }
 
 extern "C" int medtok_topk_search_f32(const float *xhat, const float *xsq, int64_t n, const float *what,
                                       const float *wsq, int64_t k_codes, int d, int topk, int64_t *idx, float *dist,
                                       void *ws, size_t ws_bytes, int path, void *stream)
 {
-    return search_impl(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, path, stream, nullptr);
-}
-
-// DEV probe (tools/r04/filter_probe.py): the filter kernel of one search with per-wave cycle counts of its loop segments written to
-// `probe` (uint64 [blocks][8][8] -- [blocks][4][8] for D <= 64, whose kernel has four waves; blocks = *n_blocks on return).  Same plan as the search would take, main launch only; the
-// candidate lists it writes into `ws` are discarded.
-extern "C" int medtok_debug_filter_probe(const float *xhat, const float *xsq, int64_t n, const float *what, const float *wsq, int64_t k_codes, int d,
-                                         int topk, void *ws, size_t ws_bytes, void *probe, size_t probe_bytes, int64_t *n_blocks, void *stream)
-{
-    if (topk < 2 || topk > 5) return fail("filter_probe: topk 2..5");
-    // (at D <= 64 the timed instantiation is the 128 x 64 wave-tile kernel's: size the workspace with MEDTOK_PLAN_FILTER_ROWS64_WIDE)
-    const PlanOverride ov = decode_plan(MEDTOK_PATH_F16_FILTER | MEDTOK_PLAN_FILTER_ROWS64_WIDE);
-    const FilterPlan f = plan_filter(n, k_codes, d, topk, ov);
-    const FilterWs w = filter_ws_layout(ws, n, f);
-    if (!ws || ws_bytes < w.total) return fail("filter_probe: workspace too small (%zu < %zu)", ws_bytes, w.total);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)lmin(4096, (f.n_pad * (f.dp / 8) + 255) / 256)), dim3(256), 0, s, xhat, (long)n, d, f.n_pad, f.dp, w.xh);
-    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)lmin(4096, (f.k_pad * (f.dp / 8) + 255) / 256)), dim3(256), 0, s, what, (long)k_codes, d, f.k_pad, f.dp, w.wh);
-    hipLaunchKernelGGL(wsq_max_kernel, dim3(1), dim3(1024), 0, s, wsq, (int)k_codes, w.en_max, (float *)nullptr, 0, (int *)nullptr);
-    hipLaunchKernelGGL(pad_wsq_kernel, dim3((unsigned)((f.k_pad + 255) / 256)), dim3(256), 0, s, wsq, (int)k_codes, (int)f.k_pad, w.wsqp);
-    if (f.rows64) {         // D <= 64: uint64 [blocks][4][8]
-        const size_t blocks = (size_t)f.row_tiles * f.splits;
-        if (probe_bytes < blocks * 256) return fail("filter_probe: probe buffer too small (%zu < %zu)", probe_bytes, blocks * 256);
-        if (hipMemsetAsync(probe, 0, blocks * 256, s) != hipSuccess) return fail("filter_probe: memset failed");
-        (void)set_lds_once<filter_rows64_kernel<5, true>>(R64_SMEM_BYTES);
-        hipLaunchKernelGGL((filter_rows64_kernel<5, true>), dim3((unsigned)f.row_tiles, (unsigned)f.splits), dim3(R64_THREADS), R64_SMEM_BYTES, s,
-                           w.xh, w.wh, xsq, w.wsqp, w.en_max, (long)n, (int)k_codes, d, f.codes_per_split, f.own_total, w.cand, w.cand_cnt,
-                           (unsigned long long *)probe);
-        if (n_blocks) *n_blocks = (int64_t)blocks;
-        return check_launch("filter_probe(rows64)");
-    }
-    (void)set_lds_once<filter_f16_kernel<5, false, true>>(F_SMEM_BYTES);
-    dim3 fgrid((unsigned)f.main_tiles, (unsigned)f.splits);
-    if (f.xcd_rows) fgrid = dim3((unsigned)(((f.main_tiles + 8 * f.xcd_rows - 1) / (8 * f.xcd_rows)) * 256), 1);
-    const size_t blocks = (size_t)fgrid.x * fgrid.y;
-    if (probe_bytes < blocks * 8 * 8 * 8) return fail("filter_probe: probe buffer too small (%zu < %zu)", probe_bytes, blocks * 512);
-    if (hipMemsetAsync(probe, 0, blocks * 512, s) != hipSuccess) return fail("filter_probe: memset failed");
-    hipLaunchKernelGGL((filter_f16_kernel<5, false, true>), fgrid, dim3(F_THREADS), F_SMEM_BYTES, s,
-                       w.xh, w.wh, xsq, w.wsqp, w.en_max, (long)n, (int)k_codes, f.dp, d, f.codes_per_split, f.own_total,
-                       w.cand, w.cand_cnt, (float *)probe, f.xcd_rows, f.splits, 0, (int)f.main_tiles);
-    if (n_blocks) *n_blocks = (int64_t)blocks;
-    return check_launch("filter_probe");
+    return search_impl(plan_search_call(n, k_codes, d, topk, path), xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, stream, nullptr);
 }
 
 // Test hook: byte offset, inside a filter-path search workspace, of the int32 count of rows the filter handed to the exact kernel
@@ -1447,114 +787,77 @@ extern "C" int medtok_debug_filter_probe(const float *xhat, const float *xsq, in
 // does not take the filter path.
 extern "C" size_t medtok_debug_filter_fallback_count_offset(int64_t n, int64_t k_codes, int d, int topk, int path)
 {
-    if (n <= 0 || k_codes <= 0 || resolve_path(path, n, k_codes, d, topk) != MEDTOK_PATH_F16_FILTER) return (size_t)-1;
-    const FilterWs w = filter_ws_layout((void *)256, n, plan_filter(n, k_codes, d, topk, decode_plan(path)));
+    const SearchCall c = plan_search_call(n, k_codes, d, topk, path);
+    if (c.path != MEDTOK_PATH_F16_FILTER) return (size_t)-1;
+    const FilterWs w = filter_ws_layout((void *)256, n, c.filter);
     return (size_t)((char *)w.fb_count - (char *)256);
 }
 
 // Measurement hook (bench.py --data ..., tests): what the filter pass of a finished search left in its workspace -- how many candidates
-// it shortlisted, how many of a row's lists are full, how many rows it handed to the exact kernel.  `ws` is the workspace of the
-// search call (soft_vq_ws != 0: of a medtok_soft_vq_forward*_f32 call, whose search workspace starts behind |x|^2), read after
-// the call on the same stream.  out[0] = candidates over all rows and lists, out[1] = lists at or over capacity, out[2] = rows
-// handed to the exact kernel, out[3] = lists in total (rows x owners).
-__global__ __launch_bounds__(256) void filter_stats_kernel(const int *__restrict__ cnt, long lists, const int *__restrict__ cnt_tail, long lists_tail,
-                                                           const int *__restrict__ fb_count, unsigned long long *__restrict__ out)
-{
-    unsigned long long cand = 0, full = 0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < lists + lists_tail; i += (long)gridDim.x * 256) {
-        const int c = i < lists ? cnt[i] : cnt_tail[i - lists];
-        cand += (unsigned long long)min(c, F_CAP);
-        full += c >= F_CAP ? 1ull : 0ull;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { cand += __shfl_xor(cand, off, 64); full += __shfl_xor(full, off, 64); }
-    if ((threadIdx.x & 63) == 0) { atomicAdd(&out[0], cand); atomicAdd(&out[1], full); }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { out[2] = (unsigned long long)*fb_count; out[3] = (unsigned long long)(lists + lists_tail); }
-}
-
+// it shortlisted, how many of a row's lists are full, how many rows it handed to the exact kernel (filter_stats_kernel).  `ws` is the
+// workspace of the search call (soft_vq_ws != 0: of a medtok_soft_vq_forward*_f32 call, whose search workspace starts behind |x|^2),
+// read after the call on the same stream.  out[0] = candidates over all rows and lists, out[1] = lists at or over capacity, out[2] =
+// rows handed to the exact kernel, out[3] = lists in total (rows x owners).
 extern "C" int medtok_debug_filter_stats(const void *ws, size_t ws_bytes, int soft_vq_ws, int64_t n, int64_t k_codes, int d, int topk, int path,
                                          uint64_t *out, void *stream)
 {
     if (!ws || !out || n <= 0 || k_codes <= 0) return fail("filter_stats: bad arguments");
-    if (topk < 1 || topk > 8 || resolve_path(path, n, k_codes, d, topk) != MEDTOK_PATH_F16_FILTER) return fail("filter_stats: this shape does not take the filter path");
+    const SearchCall c = plan_search_call(n, k_codes, d, topk, path);
+    if (c.path != MEDTOK_PATH_F16_FILTER) return fail("filter_stats: this shape does not take the filter path");
     const size_t head = soft_vq_ws ? align_up((size_t)n * 4, 256) : 0;
-    const FilterPlan f = plan_filter(n, k_codes, d, topk, decode_plan(path));
+    const FilterPlan &f = c.filter;
     const FilterWs w = filter_ws_layout((char *)const_cast<void *>(ws) + head, n, f);
     if (ws_bytes < head + w.total) return fail("filter_stats: workspace too small (%zu < %zu)", ws_bytes, head + w.total);
-    const long n_main = (long)lmin(n, f.main_tiles * f.row_bn), n_tail = (long)n - n_main;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(out, 0, 32, s) != hipSuccess) return fail("filter_stats: memset failed");
-    const long lists = n_main * f.own_total, lists_tail = n_tail * f.own_tail;
+    const long lists = w.n_main * f.own_total, lists_tail = w.n_tail * f.own_tail;
     hipLaunchKernelGGL(filter_stats_kernel, dim3((unsigned)lmin(1024, (lists + lists_tail + 255) / 256)), dim3(256), 0, s, w.cand_cnt, lists, w.cnt_tail, lists_tail,
                        w.fb_count, (unsigned long long *)out);
     return check_launch("filter_stats");
 }
 
 // Test hook: the filter's approximate scores s~ [n, k_codes] (same MFMA sequence as the search uses),
-// so tests can measure |s~ - s| against the bound filter_f16.h assumes.
+// so tests can measure |s~ - s| against the bound filter_f16.h assumes.  The score dump is an instantiation of the general
+// kernel (same MFMA order at any D), so both entry points force that kernel's plan whatever the depth.
+struct ScoreDumpWs { _Float16 *xh, *wh; float *en_max, *wsqp; size_t total; };
+static ScoreDumpWs score_dump_layout(void *ws, const FilterPlan &f)
+{
+    const size_t xb = align_up((size_t)f.n_pad * f.dp * 2, 256), wb = align_up((size_t)f.k_pad * f.dp * 2, 256);
+    char *b = (char *)ws;
+    return {(_Float16 *)b, (_Float16 *)(b + xb), (float *)(b + xb + wb), (float *)(b + xb + wb + 512), xb + wb + 512 + align_up((size_t)f.k_pad * 4, 256)};
+}
+static FilterPlan score_dump_plan(int64_t n, int64_t k_codes, int d)
+{
+    PlanOverride gen; gen.filter_rows64 = 0;
+    return plan_filter(n, k_codes, d, 5, gen);
+}
+
 extern "C" size_t medtok_debug_filter_scores_workspace_bytes(int64_t n, int64_t k_codes, int d)
 {
     if (n <= 0 || k_codes <= 0 || d <= 0) return 0;
-    PlanOverride gen; gen.filter_rows64 = 0;     // (the score dump is an instantiation of the general kernel: same MFMA order at any D)
-    FilterPlan f = plan_filter(n, k_codes, d, 5, gen);
-    return align_up((size_t)f.n_pad * f.dp * 2, 256) + align_up((size_t)f.k_pad * f.dp * 2, 256) + 512 + align_up((size_t)f.k_pad * 4, 256);
+    return score_dump_layout(nullptr, score_dump_plan(n, k_codes, d)).total;
 }
 
 extern "C" int medtok_debug_filter_scores_f32(const float *xhat, const float *xsq, int64_t n, const float *what, const float *wsq,
                                               int64_t k_codes, int d, float *scores, void *ws, size_t ws_bytes, void *stream)
 {
     if (n <= 0 || k_codes <= 0 || d <= 0 || (d & 3)) return fail("debug_filter_scores: bad shape");
-    PlanOverride gen; gen.filter_rows64 = 0;
-    FilterPlan f = plan_filter(n, k_codes, d, 5, gen);
-    const size_t xb = align_up((size_t)f.n_pad * f.dp * 2, 256), wb = align_up((size_t)f.k_pad * f.dp * 2, 256);
-    if (!ws || ws_bytes < xb + wb + 512 + (size_t)f.k_pad * 4) return fail("debug_filter_scores: workspace too small");
+    const FilterPlan f = score_dump_plan(n, k_codes, d);
+    const ScoreDumpWs w = score_dump_layout(ws, f);
+    if (!ws || ws_bytes < w.total) return fail("debug_filter_scores: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    _Float16 *xh = (_Float16 *)ws, *wh = (_Float16 *)((char *)ws + xb);
-    float *en_max = (float *)((char *)ws + xb + wb);
-    float *wsqp = (float *)((char *)ws + xb + wb + 512);
-    hipLaunchKernelGGL(pad_wsq_kernel, dim3((unsigned)((f.k_pad + 255) / 256)), dim3(256), 0, s, wsq, (int)k_codes, (int)f.k_pad, wsqp);
-    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)lmin(4096, (f.n_pad * (f.dp / 8) + 255) / 256)), dim3(256), 0, s, xhat, (long)n, d, f.n_pad, f.dp, xh);
-    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)lmin(4096, (f.k_pad * (f.dp / 8) + 255) / 256)), dim3(256), 0, s, what, (long)k_codes, d, f.k_pad, f.dp, wh);
-    hipLaunchKernelGGL(wsq_max_kernel, dim3(1), dim3(1024), 0, s, wsq, (int)k_codes, en_max, (float *)nullptr, 0, (int *)nullptr);
+    hipLaunchKernelGGL(pad_wsq_kernel, dim3((unsigned)((f.k_pad + 255) / 256)), dim3(256), 0, s, wsq, (int)k_codes, (int)f.k_pad, w.wsqp);
+    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)lmin(4096, (f.n_pad * (f.dp / 8) + 255) / 256)), dim3(256), 0, s, xhat, (long)n, d, f.n_pad, f.dp, w.xh);
+    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)lmin(4096, (f.k_pad * (f.dp / 8) + 255) / 256)), dim3(256), 0, s, what, (long)k_codes, d, f.k_pad, f.dp, w.wh);
+    hipLaunchKernelGGL(wsq_max_kernel, dim3(1), dim3(1024), 0, s, wsq, (int)k_codes, w.en_max, (float *)nullptr, 0, (int *)nullptr);
     (void)set_lds_once<filter_f16_kernel<5, true>>(F_SMEM_BYTES);
-    hipLaunchKernelGGL((filter_f16_kernel<5, true>), dim3((unsigned)f.row_tiles, 1), dim3(F_THREADS), F_SMEM_BYTES, s, xh, wh, xsq, wsqp, en_max,
+    hipLaunchKernelGGL((filter_f16_kernel<5, true>), dim3((unsigned)f.row_tiles, 1), dim3(F_THREADS), F_SMEM_BYTES, s, w.xh, w.wh, xsq, w.wsqp, w.en_max,
                        (long)n, (int)k_codes, f.dp, d, (int)f.k_pad, F_OWN_PER_SPLIT, (uint2 *)nullptr, (int *)nullptr, scores, 0, 1,
                        0, (int)f.row_tiles);
     return check_launch("filter_f16(dump)");
 }
 
-// ================================================================= merge of per-shard top-k lists
-// Code-sharded search (SURVEY 8e variant): every shard returns, for the same rows, its own top-k over its slice of
-// the codebook (global code ids); the exact top-k over the union is the (d, index)-lexicographic merge.
-__global__ __launch_bounds__(256) void merge_lists_kernel(const float *__restrict__ dist_parts, const int64_t *__restrict__ idx_parts,
-                                                          long n, int parts, int topk, int64_t *__restrict__ out_idx,
-                                                          float *__restrict__ out_dist)
-{
-    const long row = (long)blockIdx.x * 256 + threadIdx.x;
-    if (row >= n) return;
-    float bv[MEDTOK_MAX_TOPK];
-    long bi[MEDTOK_MAX_TOPK];
-#pragma unroll
-    for (int j = 0; j < MEDTOK_MAX_TOPK; ++j) { bv[j] = INFINITY; bi[j] = 0x7fffffffffffffffl; }
-    for (int p = 0; p < parts; ++p)
-        for (int j = 0; j < topk; ++j) {
-            const float v = dist_parts[((long)p * n + row) * topk + j];
-            const long c = idx_parts[((long)p * n + row) * topk + j];
-            // insertion by (value, index); the lists are short (parts * topk entries)
-#pragma unroll
-            for (int q = MEDTOK_MAX_TOPK - 1; q >= 0; --q) {
-                const bool before = v < bv[q] || (v == bv[q] && c < bi[q]);
-                if (before) {
-                    if (q + 1 < MEDTOK_MAX_TOPK) { bv[q + 1] = bv[q]; bi[q + 1] = bi[q]; }
-                    bv[q] = v; bi[q] = c;
-                }
-            }
-        }
-#pragma unroll
-    for (int j = 0; j < MEDTOK_MAX_TOPK; ++j)
-        if (j < topk) { out_idx[row * topk + j] = bi[j] == 0x7fffffffffffffffl ? (long)j : bi[j]; out_dist[row * topk + j] = bv[j]; }   // NaN rows: in range
-}
-
+// ================================================================= merge of per-shard top-k lists (merge_lists_kernel)
 extern "C" int medtok_merge_topk_lists_f32(const float *dist_parts, const int64_t *idx_parts, int64_t n, int parts, int topk,
                                            int64_t *idx, float *dist, void *stream)
 {
@@ -1565,70 +868,8 @@ extern "C" int medtok_merge_topk_lists_f32(const float *dist_parts, const int64_
     return check_launch("merge_topk_lists");
 }
 
-// ================================================================= soft assign
-// One wavefront per row; lanes stride the D axis in float4.
-template <int MAXK>
-__global__ __launch_bounds__(256) void soft_assign_kernel(const float *__restrict__ xref, const float *__restrict__ what,
-                                                          const int64_t *__restrict__ idx, const float *__restrict__ dist,
-                                                          long n, int d, int topk, int flags, float *__restrict__ w_out,
-                                                          float *zq_ste, long zq_stride, float *__restrict__ row_sqerr,
-                                                          const int *__restrict__ row_list, const int *__restrict__ row_count)
-{
-    const bool hard = flags & MEDTOK_ASSIGN_HARD, raw = flags & MEDTOK_ASSIGN_RAW;
-    const int lane = threadIdx.x & 63;
-    long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
-    if (row_list) {                    // only the listed rows (the filter's exact-path leftovers after a fused assignment)
-        if (row >= *row_count) return;
-        row = row_list[row];
-    }
-    float wj[MAXK];
-    long cj[MAXK];
-    if (hard) {
-        wj[0] = 1.f;
-        cj[0] = idx[row];
-    } else {
-        const float m = -dist[row * topk];
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < MAXK; ++j)
-            if (j < topk) { wj[j] = expf(-dist[row * topk + j] - m); sum += wj[j]; cj[j] = idx[row * topk + j]; }
-#pragma unroll
-        for (int j = 0; j < MAXK; ++j)
-            if (j < topk) wj[j] = wj[j] / sum;
-    }
-    if (w_out && lane < topk) {
-        float v = wj[0];
-#pragma unroll
-        for (int j = 1; j < MAXK; ++j) v = (lane == j) ? wj[j] : v;
-        w_out[row * topk + lane] = v;
-    }
-    const float *xr = xref + row * d;
-    float *out = zq_ste + row * zq_stride;
-    float se = 0.f;
-    for (int i = lane * 4; i < d; i += 256) {
-        float4 a;
-        if (hard) {
-            a = ld4(what + cj[0] * d + i);
-        } else {
-            a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int j = 0; j < MAXK; ++j)
-                if (j < topk) {
-                    const float4 e = ld4(what + cj[j] * d + i);
-                    a.x = fmaf(wj[j], e.x, a.x); a.y = fmaf(wj[j], e.y, a.y);
-                    a.z = fmaf(wj[j], e.z, a.z); a.w = fmaf(wj[j], e.w, a.w);
-                }
-        }
-        const float4 x = ld4(xr + i);
-        float4 df;
-        df.x = a.x - x.x; df.y = a.y - x.y; df.z = a.z - x.z; df.w = a.w - x.w;
-        st4(out + i, raw ? a : make_float4(x.x + df.x, x.y + df.y, x.z + df.z, x.w + df.w));
-        se = fmaf(df.x, df.x, se); se = fmaf(df.y, df.y, se); se = fmaf(df.z, df.z, se); se = fmaf(df.w, df.w, se);
-    }
-    se = wave_butterfly_sum(se);
-    if (row_sqerr && lane == 0) row_sqerr[row] = se;
-}
+// ================================================================= soft assign, fixed-order fp64 sum (assign_kernels.h)
+#include "assign_kernels.h"
 
 extern "C" int medtok_soft_assign_f32(const float *xref, const float *what, const int64_t *idx, const float *dist,
                                       int64_t n, int d, int topk, int flags, float *w, float *zq_ste, int64_t zq_stride,
@@ -1655,88 +896,20 @@ extern "C" int medtok_soft_assign_f32(const float *xref, const float *what, cons
     return check_launch("soft_assign");
 }
 
-// ================================================================= several small searches, batched (kernels next to search_f32_kernel)
-// Joins the per-split lists of a row (merge_topk_kernel<T, 64>: a wavefront per row, (d, index) total order) and does the row's soft
-// assignment at once (soft_assign_kernel's arithmetic on the values it would have read back: the same bits).
-template <int TOPK>
-__global__ __launch_bounds__(256) void merge_assign_multi_kernel(MultiSearchArgs a)
+extern "C" int medtok_sum_scale_f32(const float *vals, int64_t n, double scale, float *out, void *stream)
 {
-    const MultiSearchOne &m = a.s[blockIdx.y];
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= m.n) return;
-    const int d = a.d, topk = a.topk;
-    float bv[TOPK];
-    int bi[TOPK];
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j) { bv[j] = INFINITY; bi[j] = 0x7fffffff; }
-    for (int sp = lane; sp < m.splits; sp += 64) {
-        const long base = ((long)sp * m.n + row) * TOPK;
-#pragma unroll
-        for (int j = 0; j < TOPK; ++j) topk_insert_lex<TOPK>(bv, bi, m.pval[base + j], m.pidx[base + j]);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        float pv[TOPK];
-        int pi[TOPK];
-#pragma unroll
-        for (int j = 0; j < TOPK; ++j) { pv[j] = __shfl_xor(bv[j], off, 64); pi[j] = __shfl_xor(bi[j], off, 64); }
-#pragma unroll
-        for (int j = 0; j < TOPK; ++j) topk_insert_lex<TOPK>(bv, bi, pv[j], pi[j]);
-    }
-    long cj[TOPK];
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j) cj[j] = valid_code(bi[j], j, m.k_codes);
-    if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < TOPK; ++j)
-            if (j < topk) { m.idx[row * topk + j] = cj[j]; m.dist[row * topk + j] = bv[j]; }
-    }
-    float wj[TOPK];
-    const float mx = -bv[0];
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j)
-        if (j < topk) { wj[j] = expf(-bv[j] - mx); sum += wj[j]; }
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j)
-        if (j < topk) wj[j] = wj[j] / sum;
-    if (m.w && lane < topk) {
-        float v = wj[0];
-#pragma unroll
-        for (int j = 1; j < TOPK; ++j) v = (lane == j) ? wj[j] : v;
-        m.w[row * topk + lane] = v;
-    }
-    const float *xr = m.x + row * m.x_stride;
-    float *out = m.zq + row * m.zq_stride;
-    float se = 0.f;
-    for (int i = lane * 4; i < d; i += 256) {
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int j = 0; j < TOPK; ++j)
-            if (j < topk) {
-                const float4 e = ld4(m.what + cj[j] * d + i);
-                acc.x = fmaf(wj[j], e.x, acc.x); acc.y = fmaf(wj[j], e.y, acc.y);
-                acc.z = fmaf(wj[j], e.z, acc.z); acc.w = fmaf(wj[j], e.w, acc.w);
-            }
-        const float4 x = ld4(xr + i);
-        float4 df;
-        df.x = acc.x - x.x; df.y = acc.y - x.y; df.z = acc.z - x.z; df.w = acc.w - x.w;
-        st4(out + i, make_float4(x.x + df.x, x.y + df.y, x.z + df.z, x.w + df.w));
-        se = fmaf(df.x, df.x, se); se = fmaf(df.y, df.y, se); se = fmaf(df.z, df.z, se); se = fmaf(df.w, df.w, se);
-    }
-    if (m.row_sqerr) {                              // (soft_assign_kernel's sum: 64 strided fmaf chains joined by the xor butterfly)
-        se = wave_butterfly_sum(se);
-        if (lane == 0) m.row_sqerr[row] = se;
-    }
+    if (n < 0 || !out) return fail("sum_scale: bad args");
+    hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, vals, (long)n, scale, out);
+    return check_launch("sum_scale");
 }
 
+// ================================================================= several small searches, batched (kernels in search_f32.h)
 constexpr int64_t MS_MAX_ROWS = 4096;
 
 extern "C" int medtok_soft_vq_multi_eligible(int64_t n, int64_t k_codes, int d, int topk)
 {
     return n >= 1 && n <= MS_MAX_ROWS && k_codes >= 1 && k_codes < (1ll << 31) && d > 0 && !(d & 3) && topk >= 1 && topk <= 8 &&
-           topk <= k_codes && resolve_path(MEDTOK_PATH_AUTO, n, k_codes, d, topk) == MEDTOK_PATH_F32_MFMA;
+           topk <= k_codes && plan_search_call(n, k_codes, d, topk, MEDTOK_PATH_AUTO).path == MEDTOK_PATH_F32_MFMA;
 }
 
 // code splits of every search of a batched call: about two rounds' worth of blocks over the whole call (two 256-thread blocks are
@@ -1760,7 +933,7 @@ extern "C" size_t medtok_soft_vq_forward_multi_workspace_bytes(const medtok_sear
     if (!descs || count < 1 || count > MS_MAX) return 0;
     int splits[MS_MAX], cps[MS_MAX];
     multi_plan(descs, count, splits, cps);
-    const int tslots = topk == 1 ? 1 : (topk <= 5 ? 5 : 8);
+    const int tslots = list_slots(topk);
     size_t total = 0;
     for (int i = 0; i < count; ++i) {
         const size_t n = (size_t)(descs[i].n > 0 ? descs[i].n : 1);
@@ -1785,7 +958,7 @@ extern "C" int medtok_soft_vq_forward_multi_f32(const medtok_search_desc *descs,
     if (!ws || ws_bytes < need) return fail("soft_vq_forward_multi: workspace too small (%zu < %zu)", ws_bytes, need);
     int splits[MS_MAX], cps[MS_MAX];
     multi_plan(descs, count, splits, cps);
-    const int tslots = topk == 1 ? 1 : (topk <= 5 ? 5 : 8);
+    const int tslots = list_slots(topk);
     MultiSearchArgs a;
     memset(&a, 0, sizeof a);
     a.count = count; a.d = d; a.topk = topk;
@@ -1812,56 +985,16 @@ extern "C" int medtok_soft_vq_forward_multi_f32(const medtok_search_desc *descs,
     for (int i = 0; i < count; ++i) pflops += 2.0 * (double)descs[i].n * (double)descs[i].k_codes * (double)d;
     (void)max_tiles; (void)max_splits;
     const dim3 grid((unsigned)a.block_base[count]);          // exactly the blocks that have work, search after search
-#define MEDTOK_MS(T)                                                                                                          \
-    do {                                                                                                                      \
-        if (d % S_BK) {                                                                                                       \
-            (void)set_lds_once<search_f32_multi_kernel<T, true>>(S_LDS_BYTES);                                                \
-            hipLaunchKernelGGL((search_f32_multi_kernel<T, true>), grid, dim3(256), S_LDS_BYTES, s, a);                       \
-        } else {                                                                                                              \
-            (void)set_lds_once<search_f32_multi_kernel<T, false>>(S_LDS_BYTES);                                               \
-            hipLaunchKernelGGL((search_f32_multi_kernel<T, false>), grid, dim3(256), S_LDS_BYTES, s, a);                      \
-        }                                                                                                                     \
-        if (pa) prof_push(pa, prof_mark(s), pflops, 1);                                                                       \
-        hipLaunchKernelGGL((merge_assign_multi_kernel<T>), dim3((unsigned)((max_rows + 3) / 4), (unsigned)count), dim3(256), 0, s, a); \
-    } while (0)
-    switch (tslots) {
-    case 1: MEDTOK_MS(1); break;
-    case 5: MEDTOK_MS(5); break;
-    default: MEDTOK_MS(8); break;
-    }
-#undef MEDTOK_MS
+    dispatch_lists(tslots, d % S_BK != 0, [&](auto t, auto ktail) {
+        constexpr int T = decltype(t)::value;
+        constexpr bool KTAIL = decltype(ktail)::value;
+        (void)set_lds_once<search_f32_multi_kernel<T, KTAIL>>(S_LDS_BYTES);
+        hipLaunchKernelGGL((search_f32_multi_kernel<T, KTAIL>), grid, dim3(256), S_LDS_BYTES, s, a);
+        if (pa) prof_push(pa, prof_mark(s), pflops, 1);
+        hipLaunchKernelGGL((merge_assign_multi_kernel<T>), dim3((unsigned)((max_rows + 3) / 4), (unsigned)count), dim3(256), 0, s, a);
+        return 0;
+    });
     return check_launch("soft_vq_forward_multi");
-}
-
-// ================================================================= fixed-order fp64 sum
-__global__ __launch_bounds__(1024) void sum_scale_kernel(const float *__restrict__ v, long n, double scale, float *out)
-{
-    __shared__ double sh[1024];
-    double a = 0.0;
-    long i = threadIdx.x;
-    // same order of additions as the plain loop; eight loads in flight per thread instead of one (one block: latency-bound)
-    for (; i + 7 * 1024 < n; i += 8 * 1024) {
-        float x[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = v[i + u * 1024];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) a += (double)x[u];
-    }
-    for (; i < n; i += 1024) a += (double)v[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 512; off >= 1; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)(sh[0] * scale);
-}
-
-extern "C" int medtok_sum_scale_f32(const float *vals, int64_t n, double scale, float *out, void *stream)
-{
-    if (n < 0 || !out) return fail("sum_scale: bad args");
-    hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, vals, (long)n, scale, out);
-    return check_launch("sum_scale");
 }
 
 // ================================================================= decode: (token ids, weights) -> embedding, and its backward
@@ -2261,9 +1394,6 @@ static int attention_forward_f16s(const float *q, const int64_t *q_start, const 
 // 64-row blocks, keys from (hi, lo) fp16 images by LDS-DMA (attention_dma.h)
 static bool attention_dma_shape_ok(int d) { return d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024; }
 
-static void *g_att_dbg = nullptr;      // DEV (tools/r04): per-wave cycle counts of the pp kernel's phases
-extern "C" void medtok_debug_set_attention_probe(void *p) { g_att_dbg = p; }
-
 extern "C" int medtok_shared_kv_attention_split_f32(const float *q, const int64_t *q_start, const int64_t *q_len, const void *kv_hi, const void *kv_lo,
                                                     const int64_t *kv_start, const int64_t *kv_len, int64_t n_codes, int64_t max_q_len,
                                                     int d, float scale, float *out, void *out_hi, void *out_lo, int variant, void *stream)
@@ -2297,20 +1427,18 @@ extern "C" int medtok_shared_kv_attention_split_f32(const float *q, const int64_
         // two 32-row tiles of a code per block, run one phase apart on one copy of the keys (attention_pp.h)
         const int64_t q_pairs = (max_q_len + 63) / 64;
         if (q_pairs * (n_codes + 8) >= (1ll << 31)) return fail("shared_kv_attention_split: grid limit exceeded");
-#define MEDTOK_ATT_PP(NT, TIMED, KLO, ...)                                                                                         \
+#define MEDTOK_ATT_PP(NT, KLO, ...)                                                                                                \
     do {                                                                                                                          \
         const size_t lds = AttPP<NT>::LDS_BYTES;                                                                                  \
-        if (!set_lds_once<shared_kv_attention_pp_kernel<NT, TIMED, KLO __VA_ARGS__>>(lds)) return fail("shared_kv_attention_split: cannot reserve %zu bytes of LDS", lds); \
-        hipLaunchKernelGGL((shared_kv_attention_pp_kernel<NT, TIMED, KLO __VA_ARGS__>), dim3((unsigned)(q_pairs * ((n_codes + 7) / 8 * 8))), dim3(512), lds, s, q, q_start, \
+        if (!set_lds_once<shared_kv_attention_pp_kernel<NT, KLO __VA_ARGS__>>(lds)) return fail("shared_kv_attention_split: cannot reserve %zu bytes of LDS", lds); \
+        hipLaunchKernelGGL((shared_kv_attention_pp_kernel<NT, KLO __VA_ARGS__>), dim3((unsigned)(q_pairs * ((n_codes + 7) / 8 * 8))), dim3(512), lds, s, q, q_start, \
                            q_len, (const _Float16 *)kv_hi, (const _Float16 *)kv_lo, kv_start, kv_len, scale, out, (_Float16 *)out_hi,             \
-                           (_Float16 *)out_lo, (int)q_pairs, (int)n_codes, (unsigned long long *)g_att_dbg);                      \
+                           (_Float16 *)out_lo, (int)q_pairs, (int)n_codes);                                                        \
     } while (0)
-        const bool timed = ((variant >> 4) & 15) == 8 && g_att_dbg;   // (dev probe: tools/r04/att_probe.py)
-        if (f32_keys) { if (d == 256) MEDTOK_ATT_PP(2, false, true, , true); else if (d == 512) MEDTOK_ATT_PP(4, false, true, , true); else MEDTOK_ATT_PP(6, false, true, , true); }
-        else if (!kv_lo) { if (d == 256) MEDTOK_ATT_PP(2, false, false); else if (d == 512) MEDTOK_ATT_PP(4, false, false); else MEDTOK_ATT_PP(6, false, false); }
-        else if (d == 256) MEDTOK_ATT_PP(2, false, true); else if (d == 512) MEDTOK_ATT_PP(4, false, true);
-        else if (timed) MEDTOK_ATT_PP(6, true, true);
-        else MEDTOK_ATT_PP(6, false, true);
+        if (f32_keys) { if (d == 256) MEDTOK_ATT_PP(2, true, , true); else if (d == 512) MEDTOK_ATT_PP(4, true, , true); else MEDTOK_ATT_PP(6, true, , true); }
+        else if (!kv_lo) { if (d == 256) MEDTOK_ATT_PP(2, false); else if (d == 512) MEDTOK_ATT_PP(4, false); else MEDTOK_ATT_PP(6, false); }
+        else if (d == 256) MEDTOK_ATT_PP(2, true); else if (d == 512) MEDTOK_ATT_PP(4, true);
+        else MEDTOK_ATT_PP(6, true);
 #undef MEDTOK_ATT_PP
         if (pa) prof_push(pa, prof_mark(s), 0.0, 2);
         return check_launch("shared_kv_attention_split(pp)");
@@ -2406,19 +1534,6 @@ extern "C" size_t medtok_pack_codes_workspace_bytes(int64_t n_codes)
 extern "C" int medtok_pack_codes_checked(const void *mask, int mask_elem_bytes, int64_t n_codes, int64_t seq_len, const int64_t *batch, int64_t n_nodes,
                                          int heads, int lpt, int64_t *valid_len, int64_t *counts, int64_t *starts, int64_t *t_start, int64_t *t_len,
                                          int64_t *g_start, int64_t *g_len, int64_t *tok_start, int64_t *g_kv_len, int64_t *stats,
-                                         int64_t count_bound, int *status, void *ws, size_t ws_bytes, void *stream);
-extern "C" int medtok_pack_codes(const void *mask, int mask_elem_bytes, int64_t n_codes, int64_t seq_len, const int64_t *batch, int64_t n_nodes,
-                                 int heads, int lpt, int64_t *valid_len, int64_t *counts, int64_t *starts, int64_t *t_start, int64_t *t_len,
-                                 int64_t *g_start, int64_t *g_len, int64_t *tok_start, int64_t *g_kv_len, int64_t *stats, void *ws, size_t ws_bytes,
-                                 void *stream)
-{
-    return medtok_pack_codes_checked(mask, mask_elem_bytes, n_codes, seq_len, batch, n_nodes, heads, lpt, valid_len, counts, starts, t_start, t_len,
-                                     g_start, g_len, tok_start, g_kv_len, stats, 0, nullptr, ws, ws_bytes, stream);
-}
-
-extern "C" int medtok_pack_codes_checked(const void *mask, int mask_elem_bytes, int64_t n_codes, int64_t seq_len, const int64_t *batch, int64_t n_nodes,
-                                         int heads, int lpt, int64_t *valid_len, int64_t *counts, int64_t *starts, int64_t *t_start, int64_t *t_len,
-                                         int64_t *g_start, int64_t *g_len, int64_t *tok_start, int64_t *g_kv_len, int64_t *stats,
                                          int64_t count_bound, int *status, void *ws, size_t ws_bytes, void *stream)
 {
     if (count_bound < 0) return fail("pack_codes: count_bound=%ld must be >= 0 (0 = none)", (long)count_bound);
@@ -2444,6 +1559,15 @@ extern "C" int medtok_pack_codes_checked(const void *mask, int mask_elem_bytes, 
     hipLaunchKernelGGL(pack_lists_kernel, dim3(1), dim3(PACK_THREADS), sort ? pw * 4 : 0, s, counts32, stats32, valid_len, (long)n_codes,
                        (long)seq_len, heads, lpt, order, counts, starts, t_start, t_len, g_start, g_len, tok_start, g_kv_len, stats, (long)count_bound, status);
     return check_launch("pack_codes");
+}
+
+extern "C" int medtok_pack_codes(const void *mask, int mask_elem_bytes, int64_t n_codes, int64_t seq_len, const int64_t *batch, int64_t n_nodes,
+                                 int heads, int lpt, int64_t *valid_len, int64_t *counts, int64_t *starts, int64_t *t_start, int64_t *t_len,
+                                 int64_t *g_start, int64_t *g_len, int64_t *tok_start, int64_t *g_kv_len, int64_t *stats, void *ws, size_t ws_bytes,
+                                 void *stream)
+{
+    return medtok_pack_codes_checked(mask, mask_elem_bytes, n_codes, seq_len, batch, n_nodes, heads, lpt, valid_len, counts, starts, t_start, t_len,
+                                     g_start, g_len, tok_start, g_kv_len, stats, 0, nullptr, ws, ws_bytes, stream);
 }
 
 // the layer tail and the node mean around the attention core (attention_kernels.h)
@@ -2598,21 +1722,6 @@ extern "C" int medtok_split_half_scaled_f32(const float *src, int64_t n, int d, 
 // The 16-bit image (fp16, or bf16 with bf16 != 0) of an fp32 matrix [n, d]: row-major [n, dp] with zero columns past d, or (transpose) the
 // image of the transpose [d, dp], dp >= n, grouped along the rows like medtok_split_half_scaled_f32 -- operands of medtok_half_gemm_f32.
 static int half_image_impl(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp, int transpose, int64_t group_cols, int bf16,
-                           void *out, float *col_partials, void *stream);
-extern "C" int medtok_half_image_f32(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp, int transpose, int64_t group_cols, int bf16,
-                                     void *out, void *stream)
-{
-    return half_image_impl(src, n, d, src_stride, dp, transpose, group_cols, bf16, out, nullptr, stream);
-}
-// the transposed image and, from the same pass, col_partials [(dp + 63) / 64, d]: the sums over every 64-row tile of each column of src
-// (medtok_half_image_pair_sums_f32's, for a product that needs no row-major image of its upstream gradient)
-extern "C" int medtok_half_image_t_sums_f32(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp, int64_t group_cols, int bf16,
-                                            void *out, float *col_partials, void *stream)
-{
-    if (!col_partials) return fail("half_image_t_sums: NULL argument");
-    return half_image_impl(src, n, d, src_stride, dp, 1, group_cols, bf16, out, col_partials, stream);
-}
-static int half_image_impl(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp, int transpose, int64_t group_cols, int bf16,
                            void *out, float *col_partials, void *stream)
 {
     if (n < 0 || d <= 0 || (d & 3) || (dp & 7) || src_stride < d || (src_stride & 3) || dp < (transpose ? n : (int64_t)d))
@@ -2639,24 +1748,22 @@ static int half_image_impl(const float *src, int64_t n, int d, int64_t src_strid
     else hipLaunchKernelGGL(half_image_t_kernel<false>, grid, dim3(256), 0, s, src, (long)n, d, (long)src_stride, (long)dp, (long)group_cols, (unsigned short *)out, (unsigned short *)nullptr, 0, col_partials);
     return check_launch("half_image(transposed)");
 }
+extern "C" int medtok_half_image_f32(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp, int transpose, int64_t group_cols, int bf16,
+                                     void *out, void *stream)
+{
+    return half_image_impl(src, n, d, src_stride, dp, transpose, group_cols, bf16, out, nullptr, stream);
+}
+// the transposed image and, from the same pass, col_partials [(dp + 63) / 64, d]: the sums over every 64-row tile of each column of src
+// (medtok_half_image_pair_sums_f32's, for a product that needs no row-major image of its upstream gradient)
+extern "C" int medtok_half_image_t_sums_f32(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp, int64_t group_cols, int bf16,
+                                            void *out, float *col_partials, void *stream)
+{
+    if (!col_partials) return fail("half_image_t_sums: NULL argument");
+    return half_image_impl(src, n, d, src_stride, dp, 1, group_cols, bf16, out, col_partials, stream);
+}
 
 // both images of one matrix in one pass over it: out_plain [n, dp_plain] (zero columns past d; dp_plain <= d rounded up to 64) and
 // out_t = the transposed image of medtok_half_image_f32(transpose = 1, dp = np, group_cols)
-static int half_image_pair_impl(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp_plain, int64_t np, int64_t group_cols,
-                                int bf16, void *out_plain, void *out_t, float *col_partials, void *stream);
-extern "C" int medtok_half_image_pair_f32(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp_plain, int64_t np, int64_t group_cols,
-                                          int bf16, void *out_plain, void *out_t, void *stream)
-{
-    return half_image_pair_impl(src, n, d, src_stride, dp_plain, np, group_cols, bf16, out_plain, out_t, nullptr, stream);
-}
-// ... and, from the same pass, col_partials [(np + 63) / 64, d] fp32: the sums over every 64-row tile of each column (fixed order): the
-// column sums of src -- a Linear's bias gradient when src is its upstream gradient -- are the sum of these rows
-extern "C" int medtok_half_image_pair_sums_f32(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp_plain, int64_t np, int64_t group_cols,
-                                               int bf16, void *out_plain, void *out_t, float *col_partials, void *stream)
-{
-    if (!col_partials) return fail("half_image_pair_sums: NULL argument");
-    return half_image_pair_impl(src, n, d, src_stride, dp_plain, np, group_cols, bf16, out_plain, out_t, col_partials, stream);
-}
 static int half_image_pair_impl(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp_plain, int64_t np, int64_t group_cols,
                                 int bf16, void *out_plain, void *out_t, float *col_partials, void *stream)
 {
@@ -2674,46 +1781,27 @@ static int half_image_pair_impl(const float *src, int64_t n, int d, int64_t src_
     else hipLaunchKernelGGL(half_image_t_kernel<false>, grid, dim3(256), 0, s, src, (long)n, d, (long)src_stride, (long)np, (long)group_cols, (unsigned short *)out_t, (unsigned short *)out_plain, (int)dp_plain, col_partials);
     return check_launch("half_image_pair");
 }
+extern "C" int medtok_half_image_pair_f32(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp_plain, int64_t np, int64_t group_cols,
+                                          int bf16, void *out_plain, void *out_t, void *stream)
+{
+    return half_image_pair_impl(src, n, d, src_stride, dp_plain, np, group_cols, bf16, out_plain, out_t, nullptr, stream);
+}
+// ... and, from the same pass, col_partials [(np + 63) / 64, d] fp32: the sums over every 64-row tile of each column (fixed order): the
+// column sums of src -- a Linear's bias gradient when src is its upstream gradient -- are the sum of these rows
+extern "C" int medtok_half_image_pair_sums_f32(const float *src, int64_t n, int d, int64_t src_stride, int64_t dp_plain, int64_t np, int64_t group_cols,
+                                               int bf16, void *out_plain, void *out_t, float *col_partials, void *stream)
+{
+    if (!col_partials) return fail("half_image_pair_sums: NULL argument");
+    return half_image_pair_impl(src, n, d, src_stride, dp_plain, np, group_cols, bf16, out_plain, out_t, col_partials, stream);
+}
 
-static bool g_gemm_k32 = false;        // DEV (tools/r06): the one-pass products with 32-deep stages, as before round 6
-static bool g_gemm_by_row_tile = false; // DEV: tile ids by row tile whatever the row-tile count (bit 1 of the switch)
-extern "C" void medtok_debug_set_half_gemm_k32(int on) { g_gemm_k32 = (on & 1) != 0; g_gemm_by_row_tile = (on & 2) != 0; }
+static bool g_gemm_k32 = false;        // test hook: the one-pass products with 32-deep stages, as before round 6
+extern "C" void medtok_debug_set_half_gemm_k32(int on) { g_gemm_k32 = (on & 1) != 0; }
 
 static int split_gemm_impl(const void *a_hi, const void *a_lo, int64_t m, int lda, int a_group_cols,
                            const void *b_hi, const void *b_lo, int64_t b_rows, int ldb, int b_group_rows,
                            int n_g, int k_g, int groups, const float *bias, float unscale, const float *amax_a, const float *amax_b,
-                           float *c, int ldc, void *c_hi, void *c_lo, int ldch, void *stream, int one_pass = 0);
-
-// C = unscale * (A . B^T) + bias in ONE half-precision pass with fp32 accumulation: a [m, lda], b [b_rows, ldb] are fp16 (bf16 = 0) or
-// bf16 (bf16 = 1) matrices -- the product torch.autocast makes of an nn.Linear (train_MedTok.py:212,394); grouped as medtok_split_gemm_f16.
-extern "C" int medtok_half_gemm_f32(const void *a, int64_t m, int lda, int a_group_cols, const void *b, int64_t b_rows, int ldb, int b_group_rows,
-                                    int n_g, int k_g, int groups, const float *bias, float unscale, float *c, int ldc, int bf16, void *stream)
-{
-    return split_gemm_impl(a, a, m, lda, a_group_cols, b, b, b_rows, ldb, b_group_rows, n_g, k_g, groups, bias, unscale, nullptr, nullptr, c, ldc,
-                           nullptr, nullptr, 0, stream, bf16 ? 2 : 1);
-}
-
-extern "C" int medtok_split_gemm_scaled_f16(const void *a_hi, const void *a_lo, int64_t m, int lda, int a_group_cols, const void *b_hi, const void *b_lo,
-                                            int64_t b_rows, int ldb, int b_group_rows, int n_g, int k_g, int groups, const float *bias, float unscale,
-                                            const float *amax_a, const float *amax_b, float *c, int ldc, void *stream)
-{
-    return split_gemm_impl(a_hi, a_lo, m, lda, a_group_cols, b_hi, b_lo, b_rows, ldb, b_group_rows, n_g, k_g, groups, bias, unscale, amax_a, amax_b, c, ldc,
-                           nullptr, nullptr, 0, stream);
-}
-
-extern "C" int medtok_split_gemm_f16(const void *a_hi, const void *a_lo, int64_t m, int lda, int a_group_cols,
-                                     const void *b_hi, const void *b_lo, int64_t b_rows, int ldb, int b_group_rows,
-                                     int n_g, int k_g, int groups, const float *bias, float unscale,
-                                     float *c, int ldc, void *c_hi, void *c_lo, int ldch, void *stream)
-{
-    return split_gemm_impl(a_hi, a_lo, m, lda, a_group_cols, b_hi, b_lo, b_rows, ldb, b_group_rows, n_g, k_g, groups, bias, unscale, nullptr, nullptr,
-                           c, ldc, c_hi, c_lo, ldch, stream);
-}
-
-static int split_gemm_impl(const void *a_hi, const void *a_lo, int64_t m, int lda, int a_group_cols,
-                           const void *b_hi, const void *b_lo, int64_t b_rows, int ldb, int b_group_rows,
-                           int n_g, int k_g, int groups, const float *bias, float unscale, const float *amax_a, const float *amax_b,
-                           float *c, int ldc, void *c_hi, void *c_lo, int ldch, void *stream, int one_pass)
+                           float *c, int ldc, void *c_hi, void *c_lo, int ldch, void *stream, int one_pass = 0)
 {
     if (m < 0 || groups < 1 || n_g <= 0 || k_g <= 0 || (n_g & 3) || (k_g % G_BK) || (lda & 7) || (ldb & 7) || (a_group_cols & 7) || lda < k_g || ldb < k_g)
         return fail("split_gemm: bad shape m=%ld groups=%d n_g=%d k_g=%d lda=%d ldb=%d a_group_cols=%d (n_g %% 4 == 0, k_g %% 32 == 0, strides %% 8 == 0)",
@@ -2751,7 +1839,7 @@ static int split_gemm_impl(const void *a_hi, const void *a_lo, int64_t m, int ld
     // few row tiles (less than 0.8 of the 8-padded count: a weight-gradient product's 3 or 12, the 1 of a small batch): the dense order
     // (split_gemm.h) instead of "XCD = row tile mod 8", which would leave XCDs without a tile
     const long n_tiles = (long)p.row_tiles * p.ftiles * groups;
-    p.per_xcd = (!g_gemm_by_row_tile && p.row_tiles * 10 < row_ids * 8) ? (int)((n_tiles + 7) / 8) : 0;
+    p.per_xcd = p.row_tiles * 10 < row_ids * 8 ? (int)((n_tiles + 7) / 8) : 0;
     const long ids = p.per_xcd ? (long)p.per_xcd * 8 : row_ids * p.ftiles * groups;
     if (ids >= (1ll << 31)) return fail("split_gemm: grid too large");
     // persistent: one block per CU (a multiple of 8: the XCD round-robin; never fewer than 8 -- a CU-masked or partitioned device
@@ -2779,6 +1867,32 @@ static int split_gemm_impl(const void *a_hi, const void *a_lo, int64_t m, int ld
 #undef MEDTOK_GEMM_LAUNCH
     if (pa) prof_push(pa, prof_mark((hipStream_t)stream), 2.0 * (double)m * (double)n_g * (double)k_g * (double)groups, 4);     // fp32-equivalent flops (x3 on the fp16 pipe)
     return check_launch("split_gemm");
+}
+
+// C = unscale * (A . B^T) + bias in ONE half-precision pass with fp32 accumulation: a [m, lda], b [b_rows, ldb] are fp16 (bf16 = 0) or
+// bf16 (bf16 = 1) matrices -- the product torch.autocast makes of an nn.Linear (train_MedTok.py:212,394); grouped as medtok_split_gemm_f16.
+extern "C" int medtok_half_gemm_f32(const void *a, int64_t m, int lda, int a_group_cols, const void *b, int64_t b_rows, int ldb, int b_group_rows,
+                                    int n_g, int k_g, int groups, const float *bias, float unscale, float *c, int ldc, int bf16, void *stream)
+{
+    return split_gemm_impl(a, a, m, lda, a_group_cols, b, b, b_rows, ldb, b_group_rows, n_g, k_g, groups, bias, unscale, nullptr, nullptr, c, ldc,
+                           nullptr, nullptr, 0, stream, bf16 ? 2 : 1);
+}
+
+extern "C" int medtok_split_gemm_scaled_f16(const void *a_hi, const void *a_lo, int64_t m, int lda, int a_group_cols, const void *b_hi, const void *b_lo,
+                                            int64_t b_rows, int ldb, int b_group_rows, int n_g, int k_g, int groups, const float *bias, float unscale,
+                                            const float *amax_a, const float *amax_b, float *c, int ldc, void *stream)
+{
+    return split_gemm_impl(a_hi, a_lo, m, lda, a_group_cols, b_hi, b_lo, b_rows, ldb, b_group_rows, n_g, k_g, groups, bias, unscale, amax_a, amax_b, c, ldc,
+                           nullptr, nullptr, 0, stream);
+}
+
+extern "C" int medtok_split_gemm_f16(const void *a_hi, const void *a_lo, int64_t m, int lda, int a_group_cols,
+                                     const void *b_hi, const void *b_lo, int64_t b_rows, int ldb, int b_group_rows,
+                                     int n_g, int k_g, int groups, const float *bias, float unscale,
+                                     float *c, int ldc, void *c_hi, void *c_lo, int ldch, void *stream)
+{
+    return split_gemm_impl(a_hi, a_lo, m, lda, a_group_cols, b_hi, b_lo, b_rows, ldb, b_group_rows, n_g, k_g, groups, bias, unscale, nullptr, nullptr,
+                           c, ldc, c_hi, c_lo, ldch, stream);
 }
 
 extern "C" int medtok_shared_kv_attention_train_f32(const float *q, const int64_t *q_start, const int64_t *q_len, const float *kv,
@@ -2815,11 +1929,11 @@ extern "C" int medtok_shared_kv_attention_train_split_f32(const float *q, const 
 #define MEDTOK_ATT_PP_TRAIN(NT)                                                                                                   \
     do {                                                                                                                          \
         const size_t lds = AttPP<NT>::LDS_BYTES;                                                                                  \
-        if (!set_lds_once<shared_kv_attention_pp_kernel<NT, false, true, true, true>>(lds))                                        \
+        if (!set_lds_once<shared_kv_attention_pp_kernel<NT, true, true, true>>(lds))                                        \
             return fail("shared_kv_attention_train_split: cannot reserve %zu bytes of LDS", lds);                                 \
-        hipLaunchKernelGGL((shared_kv_attention_pp_kernel<NT, false, true, true, true>), dim3((unsigned)(q_pairs * ((n_codes + 7) / 8 * 8))), dim3(512), lds, s, \
+        hipLaunchKernelGGL((shared_kv_attention_pp_kernel<NT, true, true, true>), dim3((unsigned)(q_pairs * ((n_codes + 7) / 8 * 8))), dim3(512), lds, s, \
                            q, q_start, q_len, (const _Float16 *)kv, (const _Float16 *)nullptr, kv_start, kv_len, scale, out, (_Float16 *)nullptr,  \
-                           (_Float16 *)nullptr, (int)q_pairs, (int)n_codes, (unsigned long long *)nullptr, lse, thresh, seed, keep_scale); \
+                           (_Float16 *)nullptr, (int)q_pairs, (int)n_codes, lse, thresh, seed, keep_scale);                            \
     } while (0)
     if (d == 256) MEDTOK_ATT_PP_TRAIN(2); else if (d == 512) MEDTOK_ATT_PP_TRAIN(4); else MEDTOK_ATT_PP_TRAIN(6);
 #undef MEDTOK_ATT_PP_TRAIN
@@ -2833,49 +1947,7 @@ static int attention_backward_impl(const float *q, const int64_t *q_start, const
                                    const int64_t *kv_start, const int64_t *kv_len, int64_t n_codes, int64_t max_q_len,
                                    int64_t max_kv_len, int64_t q_rows, int64_t kv_rows, int d, float scale, float dropout_p,
                                    uint32_t seed, const float *out, const float *lse, const float *d_out, float *dq,
-                                   float *dkv, void *ws, size_t ws_bytes, void *stream, int hm, int acc_dkv = 0);
-
-extern "C" int medtok_shared_kv_attention_backward_f32(const float *q, const int64_t *q_start, const int64_t *q_len, const float *kv,
-                                                       const int64_t *kv_start, const int64_t *kv_len, int64_t n_codes, int64_t max_q_len,
-                                                       int64_t max_kv_len, int64_t q_rows, int64_t kv_rows, int d, float scale, float dropout_p,
-                                                       uint32_t seed, const float *out, const float *lse, const float *d_out, float *dq,
-                                                       float *dkv, void *ws, size_t ws_bytes, void *stream)
-{
-    return attention_backward_impl(q, q_start, q_len, kv, kv_start, kv_len, n_codes, max_q_len, max_kv_len, q_rows, kv_rows, d, scale, dropout_p, seed, out,
-                                   lse, d_out, dq, dkv, ws, ws_bytes, stream, 0);
-}
-
-// the same backward with its four matrix products in ONE half-precision pass (fp16; bf16 != 0: bf16) with fp32 accumulation -- the
-// precision class of nn.MultiheadAttention under torch.autocast (train_MedTok.py:212,394); operands, softmax rebuild and outputs fp32
-extern "C" int medtok_shared_kv_attention_backward_half_f32(const float *q, const int64_t *q_start, const int64_t *q_len, const float *kv,
-                                                            const int64_t *kv_start, const int64_t *kv_len, int64_t n_codes, int64_t max_q_len,
-                                                            int64_t max_kv_len, int64_t q_rows, int64_t kv_rows, int d, float scale, float dropout_p,
-                                                            uint32_t seed, const float *out, const float *lse, const float *d_out, float *dq,
-                                                            float *dkv, void *ws, size_t ws_bytes, int bf16, void *stream)
-{
-    return attention_backward_impl(q, q_start, q_len, kv, kv_start, kv_len, n_codes, max_q_len, max_kv_len, q_rows, kv_rows, d, scale, dropout_p, seed, out,
-                                   lse, d_out, dq, dkv, ws, ws_bytes, stream, bf16 ? 2 : 1);
-}
-
-// ... the same (mode 0: exact fp32, 1: fp16, 2: bf16 products) with dKV ADDED to what dkv already holds (accumulate_dkv != 0): the
-// layers of CrossAttention all attend to the ORIGINAL other modality (:83,86), so their key gradients land in one buffer -- no second
-// [kv_rows, d] tensor, no zero fill of it, no pass that adds the two.  Rows no block owns are then left as they are.
-extern "C" int medtok_shared_kv_attention_backward_acc_f32(const float *q, const int64_t *q_start, const int64_t *q_len, const float *kv,
-                                                           const int64_t *kv_start, const int64_t *kv_len, int64_t n_codes, int64_t max_q_len,
-                                                           int64_t max_kv_len, int64_t q_rows, int64_t kv_rows, int d, float scale, float dropout_p,
-                                                           uint32_t seed, const float *out, const float *lse, const float *d_out, float *dq,
-                                                           float *dkv, void *ws, size_t ws_bytes, int mode, int accumulate_dkv, void *stream)
-{
-    if (mode < 0 || mode > 2) return fail("shared_kv_attention_backward_acc: mode=%d must be 0 (fp32), 1 (fp16) or 2 (bf16)", mode);
-    return attention_backward_impl(q, q_start, q_len, kv, kv_start, kv_len, n_codes, max_q_len, max_kv_len, q_rows, kv_rows, d, scale, dropout_p, seed, out,
-                                   lse, d_out, dq, dkv, ws, ws_bytes, stream, mode, accumulate_dkv == 2 ? 2 : (accumulate_dkv != 0));
-}
-
-static int attention_backward_impl(const float *q, const int64_t *q_start, const int64_t *q_len, const float *kv,
-                                   const int64_t *kv_start, const int64_t *kv_len, int64_t n_codes, int64_t max_q_len,
-                                   int64_t max_kv_len, int64_t q_rows, int64_t kv_rows, int d, float scale, float dropout_p,
-                                   uint32_t seed, const float *out, const float *lse, const float *d_out, float *dq,
-                                   float *dkv, void *ws, size_t ws_bytes, void *stream, int hm, int acc_dkv)
+                                   float *dkv, void *ws, size_t ws_bytes, void *stream, int hm, int acc_dkv = 0)
 {
     if (n_codes < 0 || max_q_len < 0 || max_kv_len < 0 || q_rows < 0 || kv_rows < 0) return fail("shared_kv_attention_backward: bad sizes");
     if (!attention_shape_ok(d)) return fail("shared_kv_attention_backward: d=%d must be 64 or a multiple of 128, at most 768", d);
@@ -2930,6 +2002,42 @@ static int attention_backward_impl(const float *q, const int64_t *q_start, const
 #undef MEDTOK_ATT_BWD
     if (pa_bwd) prof_push(pa_bwd, prof_mark(s), 0.0, 3);     // dQ + dKV; the caller prices the pair (ragged counts live on the device)
     return check_launch("shared_kv_attention_backward");
+}
+
+extern "C" int medtok_shared_kv_attention_backward_f32(const float *q, const int64_t *q_start, const int64_t *q_len, const float *kv,
+                                                       const int64_t *kv_start, const int64_t *kv_len, int64_t n_codes, int64_t max_q_len,
+                                                       int64_t max_kv_len, int64_t q_rows, int64_t kv_rows, int d, float scale, float dropout_p,
+                                                       uint32_t seed, const float *out, const float *lse, const float *d_out, float *dq,
+                                                       float *dkv, void *ws, size_t ws_bytes, void *stream)
+{
+    return attention_backward_impl(q, q_start, q_len, kv, kv_start, kv_len, n_codes, max_q_len, max_kv_len, q_rows, kv_rows, d, scale, dropout_p, seed, out,
+                                   lse, d_out, dq, dkv, ws, ws_bytes, stream, 0);
+}
+
+// the same backward with its four matrix products in ONE half-precision pass (fp16; bf16 != 0: bf16) with fp32 accumulation -- the
+// precision class of nn.MultiheadAttention under torch.autocast (train_MedTok.py:212,394); operands, softmax rebuild and outputs fp32
+extern "C" int medtok_shared_kv_attention_backward_half_f32(const float *q, const int64_t *q_start, const int64_t *q_len, const float *kv,
+                                                            const int64_t *kv_start, const int64_t *kv_len, int64_t n_codes, int64_t max_q_len,
+                                                            int64_t max_kv_len, int64_t q_rows, int64_t kv_rows, int d, float scale, float dropout_p,
+                                                            uint32_t seed, const float *out, const float *lse, const float *d_out, float *dq,
+                                                            float *dkv, void *ws, size_t ws_bytes, int bf16, void *stream)
+{
+    return attention_backward_impl(q, q_start, q_len, kv, kv_start, kv_len, n_codes, max_q_len, max_kv_len, q_rows, kv_rows, d, scale, dropout_p, seed, out,
+                                   lse, d_out, dq, dkv, ws, ws_bytes, stream, bf16 ? 2 : 1);
+}
+
+// ... the same (mode 0: exact fp32, 1: fp16, 2: bf16 products) with dKV ADDED to what dkv already holds (accumulate_dkv != 0): the
+// layers of CrossAttention all attend to the ORIGINAL other modality (:83,86), so their key gradients land in one buffer -- no second
+// [kv_rows, d] tensor, no zero fill of it, no pass that adds the two.  Rows no block owns are then left as they are.
+extern "C" int medtok_shared_kv_attention_backward_acc_f32(const float *q, const int64_t *q_start, const int64_t *q_len, const float *kv,
+                                                           const int64_t *kv_start, const int64_t *kv_len, int64_t n_codes, int64_t max_q_len,
+                                                           int64_t max_kv_len, int64_t q_rows, int64_t kv_rows, int d, float scale, float dropout_p,
+                                                           uint32_t seed, const float *out, const float *lse, const float *d_out, float *dq,
+                                                           float *dkv, void *ws, size_t ws_bytes, int mode, int accumulate_dkv, void *stream)
+{
+    if (mode < 0 || mode > 2) return fail("shared_kv_attention_backward_acc: mode=%d must be 0 (fp32), 1 (fp16) or 2 (bf16)", mode);
+    return attention_backward_impl(q, q_start, q_len, kv, kv_start, kv_len, n_codes, max_q_len, max_kv_len, q_rows, kv_rows, d, scale, dropout_p, seed, out,
+                                   lse, d_out, dq, dkv, ws, ws_bytes, stream, mode, accumulate_dkv == 2 ? 2 : (accumulate_dkv != 0));
 }
 
 // The key gradient of SEVERAL attention calls over the same keys in one launch (attention_backward.h: DkvSources): every source brings its
@@ -2989,195 +2097,8 @@ extern "C" int medtok_shared_kv_attention_dkv_multi_f32(const medtok_dkv_source 
     return check_launch("shared_kv_attention_dkv_multi");
 }
 
-// ================================================================= EMA statistics
-// bins: integer histogram.  embed_sum: rows are ordered by (code, row) with a stable LSD radix
-// sort (8-bit digits), then one wavefront per code adds its rows in increasing row order.
-constexpr int SORT_BLOCKS = 64;        // x 4 waves = 256 sorting waves (the digit x wave count table is scanned by ONE block)
-constexpr int SORT_WAVES = SORT_BLOCKS * 4;
-
-// ids outside [0, K) are clamped (same clamp in the sort) so the layout stays consistent
-__device__ __forceinline__ uint32_t clamp_code(int64_t c, int k_codes)
-{
-    return (uint32_t)(c < 0 ? 0 : (c >= k_codes ? k_codes - 1 : c));
-}
-
-__global__ __launch_bounds__(256) void hist_kernel(const int64_t *__restrict__ idx, long n, int k_codes, int *__restrict__ counts)
-{
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-        atomicAdd(&counts[clamp_code(idx[i], k_codes)], 1);
-}
-
-// exclusive scan of counts[0..k) -> offsets[0..k] (single block, fixed order).  A thread owns 16 consecutive entries of each of
-// up to four 16384-entry slabs per pass (a wave's loads cover 4 KB of consecutive memory): per-thread sums, a shuffle scan inside
-// the wave, one scan of the 64 (slab, wave) totals by wave 0, then the entries are written with their running offsets.  (The first
-// form gave every thread one long contiguous chunk -- 64 lanes 256 bytes apart -- and took 30-40 us for the 65536-entry digit
-// table of a radix pass.)
-__global__ __launch_bounds__(1024) void scan_kernel(const int *__restrict__ counts, int k, int *__restrict__ offsets)
-{
-    constexpr int PER = 16, SLABS = 4;
-    __shared__ int wave_tot[SLABS * 16], wave_pre[SLABS * 16], carry_s;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const bool vec = ((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(offsets)) & 15) == 0;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (int base = 0; base < k; base += SLABS * 1024 * PER) {
-        int v[SLABS][PER], incl[SLABS], sum[SLABS];
-#pragma unroll
-        for (int j = 0; j < SLABS; ++j) {
-            const int start = base + (j * 1024 + t) * PER;
-            if (vec && start + PER <= k) {
-#pragma unroll
-                for (int c = 0; c < PER / 4; ++c) {
-                    const int4 q = *reinterpret_cast<const int4 *>(counts + start + 4 * c);
-                    v[j][4 * c] = q.x; v[j][4 * c + 1] = q.y; v[j][4 * c + 2] = q.z; v[j][4 * c + 3] = q.w;
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < PER; ++c) v[j][c] = start + c < k ? counts[start + c] : 0;
-            }
-            int sm = 0;
-#pragma unroll
-            for (int c = 0; c < PER; ++c) sm += v[j][c];
-            sum[j] = sm;
-            int in = sm;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int o = __shfl_up(in, off, 64);
-                if (lane >= off) in += o;
-            }
-            incl[j] = in;
-            if (lane == 63) wave_tot[j * 16 + wave] = in;
-        }
-        __syncthreads();
-        if (t < 64) {                                   // the 64 (slab, wave) totals in order
-            const int carry = carry_s;                  // (only this wave touches carry_s inside the loop: read, then written below, in program order)
-            const int x = wave_tot[t];
-            int in = x;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int o = __shfl_up(in, off, 64);
-                if (lane >= off) in += o;
-            }
-            wave_pre[t] = carry + in - x;
-            if (t == 63) carry_s = carry + in;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < SLABS; ++j) {
-            const int start = base + (j * 1024 + t) * PER;
-            int run = wave_pre[j * 16 + wave] + incl[j] - sum[j];
-            if (vec && start + PER <= k) {
-#pragma unroll
-                for (int c = 0; c < PER / 4; ++c) {
-                    int4 o;
-                    o.x = run; o.y = o.x + v[j][4 * c]; o.z = o.y + v[j][4 * c + 1]; o.w = o.z + v[j][4 * c + 2];
-                    run = o.w + v[j][4 * c + 3];
-                    *reinterpret_cast<int4 *>(offsets + start + 4 * c) = o;
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < PER; ++c)
-                    if (start + c < k) { offsets[start + c] = run; run += v[j][c]; }
-            }
-        }
-        __syncthreads();                                // wave_tot / wave_pre are reused by the next pass
-    }
-    if (t == 0) offsets[k] = carry_s;
-}
-
-__device__ __forceinline__ void wave_chunk(long n, int gw, long &lo, long &hi)
-{
-    const long per = ((n + SORT_WAVES - 1) / SORT_WAVES + 63) / 64 * 64;
-    lo = min(n, (long)gw * per);
-    hi = min(n, lo + per);
-}
-
-// pass 0 reads keys from idx (payload = position); later passes read (key,payload) pairs
-template <bool FIRST>
-__global__ __launch_bounds__(256) void radix_count_kernel(const int64_t *__restrict__ idx, const uint32_t *__restrict__ keys_in,
-                                                          long n, int k_codes, int shift, int *__restrict__ wave_counts)
-{
-    __shared__ int cnt[4][256];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, gw = blockIdx.x * 4 + w;
-    for (int i = lane; i < 256; i += 64) cnt[w][i] = 0;
-    __syncthreads();
-    long lo, hi;
-    wave_chunk(n, gw, lo, hi);
-    for (long i = lo + lane; i < hi; i += 64) {
-        const uint32_t key = FIRST ? clamp_code(idx[i], k_codes) : keys_in[i];
-        atomicAdd(&cnt[w][(key >> shift) & 255], 1);
-    }
-    __syncthreads();
-    // digit-major so the scan below yields stable destinations
-    for (int i = lane; i < 256; i += 64) wave_counts[(long)i * SORT_WAVES + gw] = cnt[w][i];
-}
-
-template <bool FIRST>
-__global__ __launch_bounds__(256) void radix_scatter_kernel(const int64_t *__restrict__ idx, const uint32_t *__restrict__ keys_in,
-                                                            const uint32_t *__restrict__ vals_in, long n, int k_codes, int shift,
-                                                            const int *__restrict__ wave_offsets, uint32_t *__restrict__ keys_out,
-                                                            uint32_t *__restrict__ vals_out)
-{
-    __shared__ int base[4][256];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, gw = blockIdx.x * 4 + w;
-    for (int i = lane; i < 256; i += 64) base[w][i] = wave_offsets[(long)i * SORT_WAVES + gw];
-    __syncthreads();
-    long lo, hi;
-    wave_chunk(n, gw, lo, hi);
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    for (long i0 = lo; i0 < hi; i0 += 64) {
-        const long i = i0 + lane;
-        const bool live = i < hi;
-        uint32_t key = 0, val = 0;
-        if (live) { key = FIRST ? clamp_code(idx[i], k_codes) : keys_in[i]; val = FIRST ? (uint32_t)i : vals_in[i]; }
-        const uint32_t dg = (key >> shift) & 255;
-        unsigned long long eq = __ballot(live);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const unsigned long long bal = __ballot((dg >> b) & 1);
-            eq &= ((dg >> b) & 1) ? bal : ~bal;
-        }
-        const int rank = __popcll(eq & lt_mask);
-        const int total = __popcll(eq);
-        int dst = 0;
-        if (live) dst = base[w][dg] + rank;
-        __builtin_amdgcn_wave_barrier();
-        if (live && rank == total - 1) base[w][dg] += total;   // one lane per digit group
-        __builtin_amdgcn_wave_barrier();
-        if (live) { keys_out[dst] = key; vals_out[dst] = val; }
-    }
-}
-
-// One wavefront per code: add that code's rows in increasing row order.
-__global__ __launch_bounds__(256) void segsum_kernel(const float *__restrict__ zhat, const uint32_t *__restrict__ sorted_rows,
-                                                     const int *__restrict__ offsets, int k_codes, int d,
-                                                     float *__restrict__ bins, float *__restrict__ embed_sum)
-{
-    const int lane = threadIdx.x & 63;
-    for (long code = (long)blockIdx.x * 4 + (threadIdx.x >> 6); code < k_codes; code += (long)gridDim.x * 4) {
-        const int lo = offsets[code], hi = offsets[code + 1];
-        if (lane == 0) bins[code] = (float)(hi - lo);
-        for (int i = lane * 4; i < d; i += 256) {
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-            int r = lo;
-            for (; r + 4 <= hi; r += 4) {      // 4 loads in flight, adds stay in row order
-                const float4 v0 = ld4(zhat + (long)sorted_rows[r] * d + i);
-                const float4 v1 = ld4(zhat + (long)sorted_rows[r + 1] * d + i);
-                const float4 v2 = ld4(zhat + (long)sorted_rows[r + 2] * d + i);
-                const float4 v3 = ld4(zhat + (long)sorted_rows[r + 3] * d + i);
-                a.x += v0.x; a.y += v0.y; a.z += v0.z; a.w += v0.w;
-                a.x += v1.x; a.y += v1.y; a.z += v1.z; a.w += v1.w;
-                a.x += v2.x; a.y += v2.y; a.z += v2.z; a.w += v2.w;
-                a.x += v3.x; a.y += v3.y; a.z += v3.z; a.w += v3.w;
-            }
-            for (; r < hi; ++r) {
-                const float4 v = ld4(zhat + (long)sorted_rows[r] * d + i);
-                a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-            }
-            st4(embed_sum + code * d + i, a);
-        }
-    }
-}
+// ================================================================= EMA statistics, EMA apply, codebook usage window (ema_kernels.h)
+#include "ema_kernels.h"
 
 struct EmaWs {
     int *counts, *offsets, *wave_counts, *wave_offsets;
@@ -3233,13 +2154,6 @@ extern "C" int medtok_ema_stats_f32(const float *zhat, const int64_t *idx, int64
     return check_launch("ema_stats");
 }
 
-// bins only (eval branch of the reference, norm_ema_quantizer.py:185-188)
-__global__ __launch_bounds__(256) void counts_to_float_kernel(const int *__restrict__ counts, long k, float *__restrict__ bins)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < k) bins[i] = (float)counts[i];
-}
-
 extern "C" size_t medtok_code_histogram_workspace_bytes(int64_t k_codes)
 {
     return k_codes > 0 ? align_up((size_t)k_codes * 4, 256) : 0;
@@ -3258,61 +2172,6 @@ extern "C" int medtok_code_histogram_f32(const int64_t *idx, int64_t n, int64_t 
     return check_launch("code_histogram");
 }
 
-// ================================================================= EMA apply
-__global__ __launch_bounds__(256) void ema_apply_kernel(float *E, float *cluster_size, const float *__restrict__ bins,
-                                                        const float *__restrict__ embed_sum, int k_codes, int d, float decay, float omd)
-{
-    const int lane = threadIdx.x & 63;
-    const long code = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (code >= k_codes) return;
-    const float b = bins[code];
-    if (lane == 0) {
-        const float a0 = cluster_size[code] * decay;
-        const float a1 = b * omd;
-        cluster_size[code] = a0 + a1;
-    }
-    float *e = E + code * d;
-    const float *sm = embed_sum + code * d;
-    const bool keep = (b == 0.0f);
-    float den1 = 1.f;
-    if (!keep) {
-        float p = 0.f;
-        for (int i = lane * 4; i < d; i += 256) {
-            float4 v = ld4(sm + i);
-            v.x = v.x / b; v.y = v.y / b; v.z = v.z / b; v.w = v.w / b;
-            p = fmaf(v.x, v.x, p); p = fmaf(v.y, v.y, p); p = fmaf(v.z, v.z, p); p = fmaf(v.w, v.w, p);
-        }
-        den1 = fmaxf(sqrtf(wave_butterfly_sum(p)), 1e-12f);
-    }
-    auto mixed = [&](int i) {
-        float4 nw;
-        const float4 ev = ld4(e + i);
-        if (keep) nw = ev;
-        else {
-            nw = ld4(sm + i);
-            nw.x = (nw.x / b) / den1; nw.y = (nw.y / b) / den1; nw.z = (nw.z / b) / den1; nw.w = (nw.w / b) / den1;
-        }
-        float4 m;
-        float t0, t1;
-        t0 = ev.x * decay; t1 = nw.x * omd; m.x = t0 + t1;
-        t0 = ev.y * decay; t1 = nw.y * omd; m.y = t0 + t1;
-        t0 = ev.z * decay; t1 = nw.z * omd; m.z = t0 + t1;
-        t0 = ev.w * decay; t1 = nw.w * omd; m.w = t0 + t1;
-        return m;
-    };
-    float p = 0.f;
-    for (int i = lane * 4; i < d; i += 256) {
-        const float4 m = mixed(i);
-        p = fmaf(m.x, m.x, p); p = fmaf(m.y, m.y, p); p = fmaf(m.z, m.z, p); p = fmaf(m.w, m.w, p);
-    }
-    const float den2 = fmaxf(sqrtf(wave_butterfly_sum(p)), 1e-12f);
-    for (int i = lane * 4; i < d; i += 256) {
-        float4 m = mixed(i);
-        m.x = m.x / den2; m.y = m.y / den2; m.z = m.z / den2; m.w = m.w / den2;
-        st4(e + i, m);
-    }
-}
-
 extern "C" int medtok_ema_apply_f32(float *E, float *cluster_size, const float *bins, const float *embed_sum, int64_t k_codes,
                                     int d, float decay, float one_minus_decay, void *stream)
 {
@@ -3322,15 +2181,6 @@ extern "C" int medtok_ema_apply_f32(float *E, float *cluster_size, const float *
     return check_launch("ema_apply");
 }
 
-__global__ __launch_bounds__(256) void ema_cluster_size_kernel(float *cs, const float *__restrict__ bins, long k, float decay, float omd)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= k) return;
-    const float a0 = cs[i] * decay;
-    const float a1 = bins[i] * omd;
-    cs[i] = a0 + a1;
-}
-
 extern "C" int medtok_ema_cluster_size_f32(float *cluster_size, const float *bins, int64_t k_codes, float decay,
                                            float one_minus_decay, void *stream)
 {
@@ -3338,47 +2188,6 @@ extern "C" int medtok_ema_cluster_size_f32(float *cluster_size, const float *bin
     hipLaunchKernelGGL(ema_cluster_size_kernel, dim3((unsigned)((k_codes + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        cluster_size, bins, (long)k_codes, decay, one_minus_decay);
     return check_launch("ema_cluster_size");
-}
-
-// ================================================================= codebook usage window
-__global__ __launch_bounds__(256) void usage_shift_kernel(const float *__restrict__ win, long wlen, const int64_t *__restrict__ ids,
-                                                          long m, float *__restrict__ tmp)
-{
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < wlen; i += (long)gridDim.x * 256) {
-        float v;
-        if (m >= wlen) v = (float)ids[m - wlen + i];
-        else v = (i < wlen - m) ? win[i + m] : (float)ids[i - (wlen - m)];
-        tmp[i] = v;
-    }
-}
-
-// Distinct count without atomics on the hot words: every window entry stores 1 into its code's flag byte (all
-// writers write the same value, so the race is benign), then one block sums the n_codes + 1 flags.  (300 000 atomicOr
-// operations on a 21 000-bit map serialise on ~650 words: 1.6 ms; this form takes microseconds.)
-__global__ __launch_bounds__(256) void usage_mark_kernel(const float *__restrict__ tmp, long wlen, long n_codes, float *__restrict__ win,
-                                                         unsigned char *__restrict__ flags)
-{
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < wlen; i += (long)gridDim.x * 256) {
-        const float v = tmp[i];
-        win[i] = v;
-        long c = (long)v;
-        if (c < 0 || c >= n_codes) c = n_codes;
-        flags[c] = 1;
-    }
-}
-
-__global__ __launch_bounds__(1024) void usage_sum_kernel(const unsigned char *__restrict__ flags, long n, int *__restrict__ count)
-{
-    __shared__ int sh[1024];
-    int a = 0;
-    for (long i = threadIdx.x; i < n; i += 1024) a += flags[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 512; off >= 1; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) count[0] = sh[0];
 }
 
 extern "C" size_t medtok_usage_workspace_bytes(int64_t window_len, int64_t n_codes)
@@ -3404,72 +2213,10 @@ extern "C" int medtok_usage_update(float *window, int64_t window_len, const int6
     return check_launch("usage_update");
 }
 
-// ---- the forward's three to five window updates (:241-250: shared, text, graph, and the aug views') in ONE call of two launches
-// (twelve to twenty before: each update a memset and three launches over the 300 000-entry window).  Conceptually the updates slide
-// one window over U = [old window | ids_1 | ids_2 | ...]: after update u the window is U[off_u, off_u + W), off_u = m_1 + ... + m_u.
-// One pass over U marks every entry in the flag map of each update whose window holds it and writes the final window
-// U[M, M + W) to scratch; a second pass copies it back and sums the maps.  Same values as the updates one by one.
-constexpr int USAGE_MULTI_MAX = 6;
-struct UsageMultiArgs { const int64_t *ids[USAGE_MULTI_MAX]; long m[USAGE_MULTI_MAX]; int count; };
-
-__global__ __launch_bounds__(256) void usage_multi_mark_kernel(const float *__restrict__ win, long wlen, UsageMultiArgs a, long n_codes,
-                                                               float *__restrict__ tmp, unsigned char *__restrict__ flags)
-{
-    long total = 0;
-    for (int u = 0; u < a.count; ++u) total += a.m[u];
-    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < wlen + total; p += (long)gridDim.x * 256) {
-        float v;
-        if (p < wlen) v = win[p];
-        else {
-            long q = p - wlen;
-            int u = 0;
-            while (q >= a.m[u]) { q -= a.m[u]; ++u; }
-            v = (float)a.ids[u][q];
-        }
-        long c = (long)v;
-        if (c < 0 || c >= n_codes) c = n_codes;
-        long off = 0;
-        for (int u = 0; u < a.count; ++u) {
-            off += a.m[u];
-            if (p >= off && p < off + wlen) flags[(long)u * (n_codes + 1) + c] = 1;
-        }
-        if (p >= total) tmp[p - total] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void usage_multi_finish_kernel(const float *__restrict__ tmp, long wlen, float *__restrict__ win,
-                                                                 const unsigned char *__restrict__ flags, long n_codes, int count, int *__restrict__ counts,
-                                                                 const int *__restrict__ extra_word = nullptr)
-{
-    // (extra_word: a device word the caller wants behind the counts -- its one host read then fetches both.  A NON-ZERO word vetoes
-    // the window write: the caller's device-side input checks failed, the ids are not to be trusted, and the caller -- who sees the
-    // word with the counts -- repeats the forward on repaired inputs against the window as it was)
-    const bool veto = extra_word && extra_word[0] != 0;
-    if (extra_word && blockIdx.x == 0 && threadIdx.x == 0) counts[count] = extra_word[0];
-    if (!veto)
-        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < wlen; i += (long)gridDim.x * 256) win[i] = tmp[i];
-    const int lane = threadIdx.x & 63;
-    for (int u = 0; u < count; ++u) {
-        int part = 0;
-        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_codes + 1; i += (long)gridDim.x * 256) part += flags[(long)u * (n_codes + 1) + i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
-        if (lane == 0 && part) atomicAdd(&counts[u], part);                // (integer: exact in any order)
-    }
-}
-
 extern "C" size_t medtok_usage_multi_workspace_bytes(int64_t window_len, int64_t n_codes, int count)
 {
     if (window_len <= 0 || n_codes <= 0 || count < 1 || count > USAGE_MULTI_MAX) return 0;
     return align_up((size_t)window_len * 4, 256) + align_up((size_t)count * ((size_t)n_codes + 1), 256);
-}
-
-extern "C" int medtok_usage_update_multi_word(float *window, int64_t window_len, const int64_t *const *ids, const int64_t *m, int count, int64_t n_codes,
-                                              int32_t *counts_out, const int32_t *extra_word, void *ws, size_t ws_bytes, void *stream);
-extern "C" int medtok_usage_update_multi(float *window, int64_t window_len, const int64_t *const *ids, const int64_t *m, int count, int64_t n_codes,
-                                         int32_t *counts_out, void *ws, size_t ws_bytes, void *stream)
-{
-    return medtok_usage_update_multi_word(window, window_len, ids, m, count, n_codes, counts_out, nullptr, ws, ws_bytes, stream);
 }
 
 // ... with a device word copied behind the counts (counts_out [count + 1]): the caller's one host read of the usage counts also brings
@@ -3502,6 +2249,12 @@ extern "C" int medtok_usage_update_multi_word(float *window, int64_t window_len,
     return check_launch("usage_update_multi");
 }
 
+extern "C" int medtok_usage_update_multi(float *window, int64_t window_len, const int64_t *const *ids, const int64_t *m, int count, int64_t n_codes,
+                                         int32_t *counts_out, void *ws, size_t ws_bytes, void *stream)
+{
+    return medtok_usage_update_multi_word(window, window_len, ids, m, count, n_codes, counts_out, nullptr, ws, ws_bytes, stream);
+}
+
 // ================================================================= one-call soft VQ forward
 // l2norm + nearest codes in one call (the head of NormEMAVectorQuantizer.forward): on the filter path the fp16 image of the
 // normalised rows that the shortlist pass streams comes out of the pass that normalises them (one read of z less).
@@ -3517,11 +2270,11 @@ extern "C" int medtok_normalized_search_f32(const float *z, int64_t n, int d, co
     if (n < 0 || k_codes <= 0 || d <= 0 || (d & 3)) return fail("normalized_search: bad shape n=%ld K=%ld d=%d (d %% 4 == 0)", (long)n, (long)k_codes, d);
     if (n == 0) return 0;
     if (!z || !zhat || !zsq || !what || !wsq || !idx || !dist) return fail("normalized_search: NULL argument");
+    const SearchCall c = plan_search_call(n, k_codes, d, topk, path);
     FuseAssign fuse = {nullptr, nullptr, nullptr, 0L, false, nullptr, nullptr, false};
-    const bool filter_path = topk >= 1 && topk <= MEDTOK_MAX_TOPK && k_codes < (1ll << 31) && n < (1ll << 31) &&
-                             resolve_path(path, n, k_codes, d, topk) == MEDTOK_PATH_F16_FILTER;
+    const bool filter_path = c.path == MEDTOK_PATH_F16_FILTER && k_codes < (1ll << 31) && n < (1ll << 31);
     if (filter_path) {
-        const FilterPlan f = plan_filter(n, k_codes, d, topk, decode_plan(path));
+        const FilterPlan &f = c.filter;
         const FilterWs fw = filter_ws_layout(ws, n, f);
         if (!ws || ws_bytes < fw.total) return fail("normalized_search: workspace too small (%zu < %zu)", ws_bytes, fw.total);
         hipStream_t s = (hipStream_t)stream;
@@ -3533,19 +2286,57 @@ extern "C" int medtok_normalized_search_f32(const float *z, int64_t n, int d, co
     } else if (medtok_rownorm_f32(z, n, d, 1, zhat, zsq, stream)) {
         return 1;
     }
-    return search_impl(zhat, zsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, path, stream, filter_path ? &fuse : nullptr);
+    return search_impl(c, zhat, zsq, n, what, wsq, k_codes, d, topk, idx, dist, ws, ws_bytes, stream, filter_path ? &fuse : nullptr);
 }
+
+// the one-call forward's workspace: |x|^2 per row, then the search's
+static inline size_t soft_vq_head_bytes(int64_t n) { return align_up((size_t)n * 4, 256); }
 
 extern "C" size_t medtok_soft_vq_workspace_bytes(int64_t n, int64_t k_codes, int d, int topk, int path)
 {
     if (n <= 0) return 256;
-    return align_up((size_t)n * 4, 256) + medtok_search_workspace_bytes(n, k_codes, d, topk, path);
+    return soft_vq_head_bytes(n) + plan_search_call(n, k_codes, d, topk, path).ws_bytes;
 }
 
 static int soft_vq_forward_impl(const float *x, int64_t n, int d, const float *what, const float *wsq, int64_t k_codes,
                                 int topk, int path, float *xhat, int64_t *idx, float *dist, float *w, float *zq_ste,
                                 int64_t zq_stride, float *row_sqerr, void *ws, size_t ws_bytes, void *stream,
-                                const _Float16 *p_wh, const float *p_wsqp, const float *p_en_max);
+                                const _Float16 *p_wh, const float *p_wsqp, const float *p_en_max)
+{
+    if (n == 0) return 0;
+    const SearchCall c = plan_search_call(n, k_codes, d, topk, path);
+    const size_t head = n > 0 ? soft_vq_head_bytes(n) : 0, need = n > 0 ? head + c.ws_bytes : 256;      // (n < 0 is refused below)
+    if (!ws || ws_bytes < need) return fail("soft_vq_forward: workspace too small (%zu < %zu)", ws_bytes, need);
+    float *xsq = (float *)ws;
+    void *sws = (char *)ws + head;
+    // Without the squared-error output (its summation order is the stand-alone kernel's) the filter path's re-score kernel
+    // does the soft assignment itself, bit for bit the same, while the top-k code rows are hot in the L2.
+    if (zq_stride == 0) zq_stride = d;
+    FuseAssign fuse = {x, w, zq_ste, (long)zq_stride, false, nullptr, nullptr, false};
+    fuse.p_wh = p_wh; fuse.p_wsqp = p_wsqp; fuse.p_en_max = p_en_max;
+    const bool try_fuse = !row_sqerr && zq_ste && zq_stride >= d && !(zq_stride & 3) && topk <= 8;
+    if (try_fuse && c.path == MEDTOK_PATH_F16_FILTER && xhat && !(d & 3)) {
+        // the filter's fp16 image of the normalised rows comes out of the same pass that normalises them
+        const FilterPlan &f = c.filter;
+        const FilterWs fw = filter_ws_layout(sws, n, f);
+        hipStream_t s = (hipStream_t)stream;
+        // (the image's padding rows are written by the same launch; with a prepared codebook it also clears the count of rows the
+        // filter hands to the exact kernel -- nothing else of the search's preparation runs then)
+        launch_rownorm<true>(s, x, (long)n, d, xhat, xsq, fw.xh, f.dp, (long)f.n_pad, p_wh ? fw.fb_count : (int *)nullptr);
+        if (check_launch("rownorm(+fp16)")) return 1;
+        fuse.xh_done = true;
+        fuse.fb_zeroed = p_wh != nullptr;
+    } else if (medtok_rownorm_f32(x, n, d, 1, xhat, xsq, stream)) {
+        return 1;
+    }
+    const int rc = search_impl(c, xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, sws, ws_bytes - head, stream, try_fuse ? &fuse : nullptr);
+    if (rc) return 1;
+    if (!fuse.done) return medtok_soft_assign_f32(x, what, idx, dist, n, d, topk, 0, w, zq_ste, zq_stride, row_sqerr, stream);
+    // rows the filter handed to the exact kernel: assignment through the device-side row list (normally empty)
+    hipLaunchKernelGGL((soft_assign_kernel<8>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream,          // (the filter path: topk <= 8)
+                       x, what, idx, dist, (long)n, d, topk, 0, w, zq_ste, (long)zq_stride, (float *)nullptr, fuse.fb_rows, fuse.fb_count);
+    return check_launch("soft_assign(list)");
+}
 
 extern "C" int medtok_soft_vq_forward_f32(const float *x, int64_t n, int d, const float *what, const float *wsq, int64_t k_codes,
                                           int topk, int path, float *xhat, int64_t *idx, float *dist, float *w, float *zq_ste,
@@ -3558,7 +2349,7 @@ extern "C" int medtok_soft_vq_forward_f32(const float *x, int64_t n, int d, cons
 // ---- a codebook prepared once per weight version
 extern "C" int medtok_filter_image_width(int d)
 {
-    return d > 0 ? (int)lmax(2 * F_BK, (d + F_BK - 1) / F_BK * F_BK) : 0;
+    return d > 0 ? filter_image_dp(d) : 0;
 }
 
 extern "C" int medtok_rownorm_image_f32(const float *x, int64_t n, int d, float *xhat, float *sqn, void *image, int64_t image_rows, int dp, void *stream)
@@ -3580,12 +2371,6 @@ extern "C" int medtok_codebook_image_f32(const float *what, int64_t n, int d, vo
     hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)lmin(4096, (image_rows * (dp / 8) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, what, (long)n, d,
                        (long)image_rows, dp, (_Float16 *)image, (int *)nullptr);
     return check_launch("codebook_image");
-}
-
-extern "C" int medtok_search_resolved_path(int64_t n, int64_t k_codes, int d, int topk, int path)
-{
-    if (n <= 0 || k_codes <= 0 || d <= 0 || topk < 1 || topk > MEDTOK_MAX_TOPK) return MEDTOK_PATH_F32_MFMA;
-    return resolve_path(path, n, k_codes, d, topk);
 }
 
 extern "C" int medtok_codebook_prepare_f32(const float *wsq, const medtok_region_desc *regions, int count, void *stream)
@@ -3610,45 +2395,4 @@ extern "C" int medtok_soft_vq_forward_prepared_f32(const float *x, int64_t n, in
     if ((uintptr_t)image & 15) return fail("soft_vq_forward_prepared: the image must be 16-byte aligned");
     return soft_vq_forward_impl(x, n, d, what, wsq, k_codes, topk, path, xhat, idx, dist, w, zq_ste, zq_stride, nullptr, ws, ws_bytes, stream,
                                 (const _Float16 *)image, wsqp, en_max);
-}
-
-static int soft_vq_forward_impl(const float *x, int64_t n, int d, const float *what, const float *wsq, int64_t k_codes,
-                                int topk, int path, float *xhat, int64_t *idx, float *dist, float *w, float *zq_ste,
-                                int64_t zq_stride, float *row_sqerr, void *ws, size_t ws_bytes, void *stream,
-                                const _Float16 *p_wh, const float *p_wsqp, const float *p_en_max)
-{
-    if (n == 0) return 0;
-    const size_t need = medtok_soft_vq_workspace_bytes(n, k_codes, d, topk, path);
-    if (!ws || ws_bytes < need) return fail("soft_vq_forward: workspace too small (%zu < %zu)", ws_bytes, need);
-    float *xsq = (float *)ws;
-    void *sws = (char *)ws + align_up((size_t)n * 4, 256);
-    // Without the squared-error output (its summation order is the stand-alone kernel's) the filter path's re-score kernel
-    // does the soft assignment itself, bit for bit the same, while the top-k code rows are hot in the L2.
-    if (zq_stride == 0) zq_stride = d;
-    FuseAssign fuse = {x, w, zq_ste, (long)zq_stride, false, nullptr, nullptr, false};
-    fuse.p_wh = p_wh; fuse.p_wsqp = p_wsqp; fuse.p_en_max = p_en_max;
-    const bool try_fuse = !row_sqerr && zq_ste && zq_stride >= d && !(zq_stride & 3) && topk <= 8;
-    const bool filter_path = topk >= 1 && topk <= MEDTOK_MAX_TOPK && resolve_path(path, n, k_codes, d, topk) == MEDTOK_PATH_F16_FILTER;
-    if (try_fuse && filter_path && xhat && !(d & 3)) {
-        // the filter's fp16 image of the normalised rows comes out of the same pass that normalises them
-        const FilterPlan f = plan_filter(n, k_codes, d, topk, decode_plan(path));
-        const FilterWs fw = filter_ws_layout(sws, n, f);
-        hipStream_t s = (hipStream_t)stream;
-        // (the image's padding rows are written by the same launch; with a prepared codebook it also clears the count of rows the
-        // filter hands to the exact kernel -- nothing else of the search's preparation runs then)
-        launch_rownorm<true>(s, x, (long)n, d, xhat, xsq, fw.xh, f.dp, (long)f.n_pad, p_wh ? fw.fb_count : (int *)nullptr);
-        if (check_launch("rownorm(+fp16)")) return 1;
-        fuse.xh_done = true;
-        fuse.fb_zeroed = p_wh != nullptr;
-    } else if (medtok_rownorm_f32(x, n, d, 1, xhat, xsq, stream)) {
-        return 1;
-    }
-    const int rc = search_impl(xhat, xsq, n, what, wsq, k_codes, d, topk, idx, dist, sws, ws_bytes - align_up((size_t)n * 4, 256), path, stream,
-                               try_fuse ? &fuse : nullptr);
-    if (rc) return 1;
-    if (!fuse.done) return medtok_soft_assign_f32(x, what, idx, dist, n, d, topk, 0, w, zq_ste, zq_stride, row_sqerr, stream);
-    // rows the filter handed to the exact kernel: assignment through the device-side row list (normally empty)
-    hipLaunchKernelGGL((soft_assign_kernel<8>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream,          // (the filter path: topk <= 8)
-                       x, what, idx, dist, (long)n, d, topk, 0, w, zq_ste, (long)zq_stride, (float *)nullptr, fuse.fb_rows, fuse.fb_count);
-    return check_launch("soft_assign(list)");
 }

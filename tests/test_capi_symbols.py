@@ -95,3 +95,32 @@ def test_header_macros_agree_with_the_python_binding():
     assert ws(100000, 8192, 64, _lib.plan_path(f, filter_rows64="wide", filter_splits=2)) == ws(100000, 8192, 64, _lib.plan_path(f, filter_rows64=False, filter_splits=2))
     assert ws(100000, 8192, 64, _lib.plan_path(f, filter_rows64=True, filter_splits=2)) < ws(100000, 8192, 64, _lib.plan_path(f, filter_rows64=False, filter_splits=2))
     assert ws(100000, 8192, 16, _lib.plan_path(f, filter_splits=2)) == ws(100000, 8192, 64, _lib.plan_path(f, filter_splits=2))      # D <= 32: 64 columns
+
+
+def test_search_host_arithmetic_matches_the_recorded_table():
+    """The plan, the workspace layout and the path of a search call are derived in one place (plan_search_call in medtok_vq.hip); what the
+    four host-only queries return must be what the library returned before that, for every row of tests/golden/search_host_parent.json:
+    699 shapes over n x K x d x topk x path x the MEDTOK_PLAN_* bits the tests use, among them exact searches with a tail launch, filter
+    searches with one, and the two-pass head of k > 8.  The table was recorded without a GPU, where the planner assumes the full chip
+    (256 CUs); with a device of another CU count visible the plans differ by design and the comparison does not apply."""
+    import json
+    import pytest
+    import torch
+    from medtok_amd import _lib
+    table = json.loads((ROOT / "tests" / "golden" / "search_host_parent.json").read_text())
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != table["cus"]:
+        pytest.skip(f"the table holds the plans of a {table['cus']}-CU device; this one has {torch.cuda.get_device_properties(0).multi_processor_count}")
+    lib = _lib.load()
+    assert table["columns"] == ["n", "k_codes", "d", "topk", "path", "search_ws_bytes", "soft_vq_ws_bytes", "resolved_path", "fb_count_offset"]
+    rows = table["rows"]
+    assert len(rows) >= 300
+    none = ctypes.c_size_t(-1).value
+    seen = {"exact": 0, "filter": 0, "wide": 0}
+    for n, k, d, topk, path, ws, soft, resolved, fb in rows:
+        args = (n, k, d, topk, path)
+        assert lib.medtok_search_workspace_bytes(*args) == ws, args
+        assert lib.medtok_soft_vq_workspace_bytes(*args) == soft, args
+        assert lib.medtok_search_resolved_path(*args) == resolved, args
+        assert lib.medtok_debug_filter_fallback_count_offset(*args) == (none if fb < 0 else fb), args
+        seen["wide" if topk > 8 else "filter" if resolved == _lib.PATH_F16_FILTER else "exact"] += 1
+    assert min(seen.values()) >= 50, seen

@@ -72,7 +72,7 @@ def test_entry_points_reject_bad_arguments_without_a_gpu():
     import ctypes as C
     from medtok_amd import _lib
     lib = _lib.load()
-    assert lib.medtok_abi_version() == 3 == _lib.ABI_VERSION
+    assert lib.medtok_abi_version() == 4 == _lib.ABI_VERSION
     one = (C.c_int64 * 4)(0, 0, 0, 0), (C.c_int64 * 4)(10, 10, 10, 10)
     assert lib.medtok_decode_tokens_f32(0, 0, 0, 4, 5, 0, 10, 8, *one, 0, 0, 0, None) == 0                    # n = 0: nothing to do
     assert lib.medtok_decode_tokens_backward_f32(0, 0, 0, 0, 0, 4, 5, 0, 10, 8, *one, 16, 0, 0, 0, None) == 0

@@ -28,7 +28,8 @@ def mutate(name, src):
         t = f.read_text()
         old = '''#undef PP_MFMA16
 #undef PP_MFMA32
-    if (TIMED && dbg && lane == 0) {'''
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (gt % TPR == 0) {'''
         new = '''    // ---- EMULATION (tools/r06/build_variants.py wv_epi): the W_v,h slice through the ring + the product's MFMAs
     if (active || true) {
         const half8 ea = qh[0][0], eb = qlo[0][0];
@@ -48,7 +49,8 @@ def mutate(name, src):
     }
 #undef PP_MFMA16
 #undef PP_MFMA32
-    if (TIMED && dbg && lane == 0) {'''
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (gt % TPR == 0) {'''
         t = sub(t, old, new)
         f.write_text(t)
     else:
