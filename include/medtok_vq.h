@@ -262,6 +262,27 @@ int medtok_embed_codes_f16(const int64_t *index, const uint8_t *pad, int64_t n, 
                            int64_t num_codes, int slots, int topk, const float *what, int64_t n_codes, int d,
                            const int64_t *region_lo, const int64_t *region_size, const float *miss, void *out, int64_t out_stride,
                            int bf16, int *status, void *stream);
+/* The lookup with the consumer's projector folded in: out[p] = b + W . emb[p], emb the row medtok_embed_codes_f32 would write, without
+ * emb (every consumer of embeddings_all.npy follows the lookup with a trained nn.Linear: EHRModel_token.py:143,215-217, review.py:24,64,
+ * MedTok_QA_inference.py:138).  The lookup is linear in the codebook rows, so the caller applies W to the codebook once per weight
+ * version: table [n_rows, hp] (fp32, hp % 4 == 0) stacks one folded table per slot, P_s = what[region s] . W[:, s*d:(s+1)*d]^T, slot s in
+ * the rows [row_lo[s], row_lo[s] + row_size[s]) (row_size[s] = the size of the slot's region: ids are region-local); bias [hp];
+ * miss_row [hp] = W . miss + b, or NULL.  Per column h ONE fp32 chain: acc = bias[h], then slots ascending, then list order,
+ * acc = fmaf(weights[c, s, j], P_s[tokens[c, s, j]][h], acc).  Per position p with c = index[p]:
+ *   pad[p] != 0                          the bias row; index[p] is not interpreted, no table is read, status is not touched
+ *   0 <= c < num_codes                   the chain above; a slot with an id outside its region contributes nothing, bit s of *status
+ *   c == num_codes and miss_row != NULL  a copy of miss_row
+ *   anything else                        the bias row, and bit 4 of *status is set
+ * slots * topk <= 64.  out [n, hp], out_stride in elements (0 = hp, a multiple of 4); the _f16 sibling rounds each finished chain
+ * once (bf16 != 0: bf16), as medtok_embed_codes_f16.  Nothing traps and nothing is read back. */
+int medtok_embed_project_f32(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                             int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp,
+                             const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row, float *out,
+                             int64_t out_stride, int *status, void *stream);
+int medtok_embed_project_f16(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                             int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp,
+                             const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row, void *out,
+                             int64_t out_stride, int bf16, int *status, void *stream);
 /* The gradient of the miss row: g_miss[width] = sum of g_out[p, :] (fp32 [n, width], row stride g_stride, 0 = width) over the positions
  * with index[p] == num_codes and pad[p] == 0, added in a fixed order (per 256 consecutive positions in position order, then those
  * partial sums in order; no float atomics): two runs give the same bits.  ws from the workspace query. */

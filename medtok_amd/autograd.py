@@ -9,7 +9,9 @@ VectorQuantizer) and the tokenizer call it, and that module re-exports every nam
   - _SegmentMeanFunction, _HeadBlockDiag: the node mean of a code, the block-diagonal per-head weights;
   - _SoftVQFunction / _SoftVQMultiFunction / _DecodeFunction: a search, all searches of a forward, and decode under autograd
     (sparse backward; the code gradients summed per code without atomics);
-  - _EmbedCodesFunction: the embedding lookup over the stored token table (MedTokEmbedding) and the gradient of its miss row.
+  - _EmbedCodesFunction: the embedding lookup over the stored token table (MedTokEmbedding) and the gradient of its miss row;
+  - _EmbedProjectFunction: that lookup with the consumer's projector folded into the tables (forward on embed_project_kernel; dW, db
+    and the miss row's gradient in a fixed order); _SmallLinearFunction / small_linear: y = x W^T + b on the exact fp32 product.
 """
 from __future__ import annotations
 
@@ -554,6 +556,92 @@ class _EmbedCodesFunction(torch.autograd.Function):
         index, pad_mask = ctx.saved_tensors
         g_miss = ops.embed_codes_miss_grad(g, index, ctx.num_codes, pad_mask) if ctx.needs_input_grad[0] else None
         return g_miss, None, None, None, None, None, None, None, None
+
+
+class _SmallLinearFunction(torch.autograd.Function):
+    """y = x W^T + b under autograd on the library's exact fp32 product (ops.small_gemm: one fmaf chain per entry, any shape): what
+    MedTokEmbedding puts behind the lookup where the projector is not folded into the tables.  dX = dY W, dW = dY^T X, db = the column
+    sum of dY; fp32 in and out; no float atomics anywhere (two runs give the same bits)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        xf, wf = x.detach().float().contiguous(), w.detach().float().contiguous()
+        ctx.save_for_backward(xf, wf)
+        ctx.has_bias = b is not None
+        if xf.shape[0] == 0:
+            return xf.new_zeros(0, wf.shape[0])
+        y = ops.small_gemm(xf, wf, trans_b=True)
+        return y if b is None else y.add_(b.detach().float())
+
+    @staticmethod
+    def backward(ctx, dy):
+        xf, wf = ctx.saved_tensors
+        dyf = dy.float().contiguous()
+        if xf.shape[0] == 0:
+            return (torch.zeros_like(xf) if ctx.needs_input_grad[0] else None, torch.zeros_like(wf) if ctx.needs_input_grad[1] else None,
+                    wf.new_zeros(wf.shape[0]) if ctx.has_bias and ctx.needs_input_grad[2] else None)
+        dx = ops.small_gemm(dyf, wf) if ctx.needs_input_grad[0] else None
+        dw = ops.small_gemm(dyf, xf, trans_a=True) if ctx.needs_input_grad[1] else None
+        db = dyf.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dx, dw, db
+
+
+def small_linear(x, w, b=None):
+    return _SmallLinearFunction.apply(x, w, b)
+
+
+EMBED_PROJECT_GRAD_CHUNK = 16384          # positions per recomputed block of embeddings in _EmbedProjectFunction.backward
+
+
+class _EmbedProjectFunction(torch.autograd.Function):
+    """projector(MedTokEmbedding lookup) with a frozen codebook under autograd.  Forward: embed_project_kernel over the folded tables
+    (`folded` = ops.fold_projector's result, built from detached tensors: constants of this node).  Backward, from g [n, Hp] (the
+    padding columns dropped), deterministic and without float atomics:
+      dW        blocks of EMBED_PROJECT_GRAD_CHUNK positions in order: emb = embed_codes(...) fp32 recomputed (the only temporary:
+                chunk x S * d floats), dW += g_block^T . emb by the exact fp32 product;
+      db        the column sum of g (padded positions are the bias row: they count);
+      d miss    (sum of g over the unpadded miss positions, embed_codes_miss_grad at width H) . W.
+    A sorted per-code scatter form of dW (G_s^T . what_s over the folded tables' rows) is not built: DESIGN.md section 10."""
+
+    @staticmethod
+    def forward(ctx, w, b, miss, index, pad_mask, tokens, weights, what, regions, e_dim, folded, out_dtype, status):
+        table, row_regions, bias, miss_row = folded
+        out = ops.embed_project(index, tokens, weights, table, row_regions, bias, miss_row=miss_row, pad_mask=pad_mask, out_dtype=out_dtype,
+                                status=status)
+        ctx.save_for_backward(w, miss, index, pad_mask, tokens, weights, what)
+        ctx.cfg = (tuple(regions), int(e_dim), b is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        w, miss, index, pad_mask, tokens, weights, what = ctx.saved_tensors
+        regions, e, has_bias = ctx.cfg
+        h, s, d = w.shape[0], len(regions), what.shape[1]
+        n = index.numel()
+        g = g.reshape(n, -1)[:, :h].float().contiguous()
+        index = index.reshape(-1)
+        pad_mask = None if pad_mask is None else pad_mask.reshape(-1)
+        wf = w.detach().float().contiguous()
+        dw = db = dmiss = None
+        if ctx.needs_input_grad[0]:
+            miss_d = None
+            if miss is not None:
+                miss_d = miss.detach().reshape(s, e)
+                miss_d = (torch.nn.functional.pad(miss_d, (0, d - e)) if d != e else miss_d).reshape(-1).contiguous()
+            dw = torch.zeros_like(wf)
+            for r0 in range(0, n, EMBED_PROJECT_GRAD_CHUNK):
+                r1 = min(n, r0 + EMBED_PROJECT_GRAD_CHUNK)
+                emb = ops.embed_codes(index[r0:r1], tokens, weights, what, regions, miss=miss_d,
+                                      pad_mask=None if pad_mask is None else pad_mask[r0:r1])
+                if d != e:
+                    emb = emb.view(r1 - r0, s, d)[:, :, :e].reshape(r1 - r0, s * e)
+                dw.add_(ops.small_gemm(g[r0:r1], emb, trans_a=True))
+        if has_bias and ctx.needs_input_grad[1]:
+            db = g.sum(0)
+        if miss is not None and ctx.needs_input_grad[2]:
+            g_rows = ops.embed_codes_miss_grad(g, index, tokens.shape[0], pad_mask) if n else g.new_zeros(h)
+            dmiss = ops.small_gemm(g_rows.view(1, h), wf).reshape(miss.shape)
+        return (dw, db, dmiss) + (None,) * 10
 
 
 def _lib_multi_max():

@@ -150,3 +150,92 @@ __global__ __launch_bounds__(256) void embed_miss_grad_sum_kernel(const float *_
     for (long ch = 0; ch < chunks; ++ch) acc = acc + partial[ch * width + col];
     g_miss[col] = acc;
 }
+
+// The lookup with the consumer's projector folded in: out[p] = b + W . emb[p] without emb.  The lookup is linear in the codebook
+// rows, so the projector is applied to the codebook once per weight version (ops.fold_projector: P_s = what[region_s] . W_s^T, one
+// [K_s, hp] table per slot, stacked in one buffer `table` with the slots' row offsets in reg.lo) and a position is
+//   out[p, h] = bias[h] + sum_s sum_j weights[c, s, j] * P_s[tokens[c, s, j], h]
+// One item = one position; all slots land in one output row.  LANES = 16, 32 or 64 lanes own it: lane i < slots * topk <= LANES loads
+// entry i of the code's ids and weights once (they are consecutive in memory), a shuffle hands them round, and the lanes cover the hp
+// columns as float4 (hp % 4 == 0; the host pads).  Per column ONE fp32 chain in a fixed order: acc = bias[h], then slots ascending,
+// then list order, acc = fmaf(w, P_s[id][h], acc); the k gathers of a slot are issued before its first fmaf.  Per position p with
+// c = index[p] -- what projector(embed_codes(...)) gives:
+//   pad[p] != 0               the bias row; index[p] is not read, nor are the tables, and status is not touched
+//   0 <= c < num_codes        the chain above (a slot with an id outside its region contributes nothing, bit `slot` of *status)
+//   c == num_codes, miss_row  a copy of miss_row [hp] (W . miss + b, made with the tables)
+//   anything else             the bias row, bit 4 of *status
+// No index and no id forms an address before it has been checked; every product with c is 64-bit.  The shuffles run with every lane
+// of the wavefront active (the column loop's trip count is uniform; only loads, fmafs and stores are predicated).
+template <int LANES, int MAXK, typename OUT>
+__global__ __launch_bounds__(256) void embed_project_kernel(const int64_t *__restrict__ index, const uint8_t *__restrict__ pad, long n,
+                                                            const int64_t *__restrict__ tokens, const float *__restrict__ weights, long num_codes,
+                                                            int slots, int topk, const float *__restrict__ table, int hp, DecodeRegions reg,
+                                                            const float *__restrict__ bias, const float *__restrict__ miss_row,
+                                                            OUT *__restrict__ out, long out_stride, int *status)
+{
+    static_assert(LANES == 16 || LANES == 32 || LANES == 64, "a group is a power-of-two part of a wavefront");
+    const int lane = threadIdx.x & 63, sub = threadIdx.x & (LANES - 1), base = lane & ~(LANES - 1);
+    long pos = (long)blockIdx.x * (256 / LANES) + threadIdx.x / LANES;
+    const bool live = pos < n;
+    if (!live) pos = 0;
+    // what this position is: the lanes of a group agree (one address each)
+    const bool padded = !live || (pad && pad[pos] != 0);
+    const long c = padded ? 0 : index[pos];
+    const bool is_code = !padded && c >= 0 && c < num_codes;
+    const bool is_miss = !padded && miss_row && c == num_codes;
+    if (!padded && !is_code && !is_miss && sub == 0 && status) atomicOr(status, 1 << MEDTOK_EMBED_BAD_INDEX_BIT);
+    const int entries = slots * topk;                             // <= LANES (checked on the host)
+    const int eslot = sub / topk;                                 // the slot of this lane's entry
+    long lo = reg.lo[0], size = reg.size[0];
+#pragma unroll
+    for (int s = 1; s < MEDTOK_DECODE_MAX_SLOTS; ++s)
+        if (eslot == s) { lo = reg.lo[s]; size = reg.size[s]; }
+    long id = 0;
+    float wv = 0.f;
+    if (is_code && sub < entries) {
+        const long at = c * entries + sub;                        // 64-bit: c < num_codes was checked above
+        id = tokens[at];
+        wv = weights[at];
+    }
+    const bool bad_lane = id < 0 || id >= size;                   // (a lane without an entry holds 0: in range, size >= 1)
+    const unsigned long long votes = __ballot(bad_lane);
+    const unsigned long long mine = LANES == 64 ? votes : (votes >> base) & ((1ull << (LANES & 63)) - 1ull);
+    const int row = bad_lane ? 0 : (int)(lo + id);                // lo + size <= rows of the table < 2^31 (checked on the host)
+    int bad_slots = 0;
+#pragma unroll
+    for (int s = 0; s < MEDTOK_DECODE_MAX_SLOTS; ++s)
+        if (s < slots && ((mine >> (s * topk)) & ((1ull << topk) - 1ull)) != 0ull) bad_slots |= 1 << s;
+    if (bad_slots && sub == 0 && status) atomicOr(status, bad_slots);      // (bad implies is_code: only such groups loaded an id)
+    const float *first = is_miss ? miss_row : bias;
+    OUT *dst = out + pos * out_stride;
+    for (int i0 = 0; i0 < hp; i0 += LANES * 4) {                  // uniform over the wavefront: the shuffles below see every lane
+        const int i = i0 + sub * 4;
+        const bool on = live && i < hp;
+        float4 a = on ? ld4(first + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int s = 0; s < MEDTOK_DECODE_MAX_SLOTS; ++s) {
+            if (s >= slots) break;
+            int rj[MAXK];
+            float wj[MAXK];
+#pragma unroll
+            for (int j = 0; j < MAXK; ++j) {
+                const int from = base + (j < topk ? s * topk + j : 0);
+                rj[j] = __shfl(row, from, 64);
+                wj[j] = __shfl(wv, from, 64);
+            }
+            if (on && is_code && !(bad_slots >> s & 1)) {
+                float4 e[MAXK];
+#pragma unroll
+                for (int j = 0; j < MAXK; ++j)                    // the k gathers of this slot: in flight together
+                    if (j < topk) e[j] = ld4(table + (long)rj[j] * hp + i);
+#pragma unroll
+                for (int j = 0; j < MAXK; ++j)
+                    if (j < topk) {
+                        a.x = fmaf(wj[j], e[j].x, a.x); a.y = fmaf(wj[j], e[j].y, a.y);
+                        a.z = fmaf(wj[j], e[j].z, a.z); a.w = fmaf(wj[j], e[j].w, a.w);
+                    }
+            }
+        }
+        if (on) embed_store4(dst + i, a);
+    }
+}

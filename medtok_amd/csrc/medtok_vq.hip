@@ -1114,6 +1114,57 @@ extern "C" int medtok_embed_codes_f16(const int64_t *index, const uint8_t *pad, 
                                         region_size, miss, (_Float16 *)out, out_stride, status, stream);
 }
 
+// both output widths of medtok_embed_project_*: the lookup with the projector folded into per-slot tables (embed_project_kernel)
+template <typename OUT>
+static int embed_project_launch(const char *fn, const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                                int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp, const int64_t *row_lo,
+                                const int64_t *row_size, const float *bias, const float *miss_row, OUT *out, int64_t out_stride, int *status,
+                                void *stream)
+{
+    DecodeRegions reg;
+    if (int rc = decode_args(fn, n, slots, topk, n_rows, hp, row_lo, row_size, reg)) return rc;
+    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
+    if (slots * topk > 64) return fail("%s: slots * topk = %d entries per code exceed one wavefront", fn, slots * topk);
+    if (out_stride == 0) out_stride = hp;
+    if (out_stride < hp || (out_stride & 3)) return fail("%s: out_stride must be >= hp and a multiple of 4", fn);
+    if (n == 0) return 0;
+    if (!index || !tokens || !weights || !table || !bias || !out) return fail("%s: index, tokens, weights, table, bias and out are required", fn);
+    hipStream_t s = (hipStream_t)stream;
+    // the smallest group that holds the code's slots * topk entries and, up to a wavefront, covers the row in one float4 pass
+    int lanes = 16;
+    while (lanes < 64 && (lanes < slots * topk || lanes * 4 < hp)) lanes *= 2;
+#define MEDTOK_PROJECT_LAUNCH(LANES, MAXK)                                                                                               \
+    hipLaunchKernelGGL((embed_project_kernel<LANES, MAXK, OUT>), dim3((unsigned)((n + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s, \
+                       index, pad, (long)n, tokens, weights, (long)num_codes, slots, topk, table, hp, reg, bias, miss_row, out,          \
+                       (long)out_stride, status)
+#define MEDTOK_PROJECT_LANES(LANES) do { if (topk <= 8) MEDTOK_PROJECT_LAUNCH(LANES, 8); else MEDTOK_PROJECT_LAUNCH(LANES, MEDTOK_MAX_TOPK); } while (0)
+    if (lanes == 16) MEDTOK_PROJECT_LANES(16); else if (lanes == 32) MEDTOK_PROJECT_LANES(32); else MEDTOK_PROJECT_LANES(64);
+#undef MEDTOK_PROJECT_LANES
+#undef MEDTOK_PROJECT_LAUNCH
+    return check_launch(fn);
+}
+
+extern "C" int medtok_embed_project_f32(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                                        int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp,
+                                        const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row, float *out,
+                                        int64_t out_stride, int *status, void *stream)
+{
+    return embed_project_launch<float>("embed_project", index, pad, n, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo, row_size,
+                                       bias, miss_row, out, out_stride, status, stream);
+}
+
+extern "C" int medtok_embed_project_f16(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
+                                        int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp,
+                                        const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row, void *out,
+                                        int64_t out_stride, int bf16, int *status, void *stream)
+{
+    if (bf16)
+        return embed_project_launch<__bf16>("embed_project_f16(bf16)", index, pad, n, tokens, weights, num_codes, slots, topk, table, n_rows, hp,
+                                            row_lo, row_size, bias, miss_row, (__bf16 *)out, out_stride, status, stream);
+    return embed_project_launch<_Float16>("embed_project_f16", index, pad, n, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo,
+                                          row_size, bias, miss_row, (_Float16 *)out, out_stride, status, stream);
+}
+
 extern "C" size_t medtok_embed_codes_miss_grad_workspace_bytes(int64_t n, int width)
 {
     if (n < 0 || width < 1) return 0;

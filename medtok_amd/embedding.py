@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import _EmbedCodesFunction
+from .autograd import _EmbedCodesFunction, _EmbedProjectFunction, small_linear
 
 DEFAULT_TYPES = ("text", "graph", "shared", "shared")
 
@@ -45,10 +45,30 @@ class MedTokEmbedding(nn.Module):
     subtracts the region offsets once, here.  miss_row: keep `miss_emb`, an nn.Parameter [1, S * e_dim] initialised randn as the
     reference's, served at index num_codes (`miss_index`); without it that index is an error.  freeze_codebook=True (the
     reference's table is a constant): the only gradient is miss_emb's; False: codebook.weight gets its gradient too, where it
-    requires one (off the hot path: composed from quantizer.decode on the gathered rows)."""
+    requires one (off the hot path: composed from quantizer.decode on the gathered rows).
+
+    projector: the nn.Linear(S * e_dim, H) every consumer of the reference puts behind the lookup (`projector(med_code_emb[data.x])`,
+    EHRModel_token.py:143,215-217); it becomes a submodule (its parameters train and travel with this module) and forward returns
+    projector(embedding) [..., H].  The lookup is linear in the codebook rows, so the projector can be applied to the codebook once
+    per weight version instead of to every position (ops.fold_projector / ops.embed_project: the [positions, S * e_dim] activation
+    never exists).  fold=True / False forces that path / the lookup followed by the dense product; fold=None folds when the
+    projector narrows (H < S * e_dim), the tables fit FOLD_MAX_BYTES and either the cached tables are valid or positions * S >= 3 x the
+    tables' rows (fold_rule, where the measurements behind it are given).  The folded tables are
+    cached per (normalised codebook entry, version and storage of projector.weight, projector.bias and miss_emb); `fold_builds`
+    counts how often they were built.  The quantizer caches its normalised codebook in eval mode only: while it is in train() mode
+    (e.g. as a submodule of a model that was sent .train()) every call normalises afresh, so the key changes and the tables are
+    refolded on every call, and fold=None never sees a valid cache; keep a frozen quantizer in eval().  Without a projector nothing
+    here changes."""
+
+    # The memory budget of the folded tables (sum of the slots' region sizes x H rounded up to 4 x 4 bytes; 134 MB for a 256-wide
+    # projector over cfg 3's 49,152 codes): above it fold=None takes the lookup followed by the dense product.  Chosen by size alone:
+    # no table near it has been timed (DESIGN.md section 7.1d).
+    FOLD_MAX_BYTES = 1 << 30
+    # fold=None builds the tables for a call only from positions * S >= FOLD_COLD_FACTOR * rows (measured, section 7.1d: see fold_rule)
+    FOLD_COLD_FACTOR = 3
 
     def __init__(self, quantizer, tokens, weights, types=DEFAULT_TYPES, miss_row: bool = True, freeze_codebook: bool = True,
-                 global_ids: bool = False):
+                 global_ids: bool = False, projector=None, fold=None):
         super().__init__()
         kinds = (types,) if isinstance(types, str) else tuple(types)
         if not 1 <= len(kinds) <= ops.DECODE_MAX_SLOTS or any(t not in quantizer.DECODE_TYPES for t in kinds):
@@ -79,6 +99,20 @@ class MedTokEmbedding(nn.Module):
             self.miss_emb = nn.Parameter(torch.randn(1, self.embedding_dim, device=dev))
         else:
             self.register_parameter("miss_emb", None)
+        if fold is not None and not isinstance(fold, bool):
+            raise ValueError(f"MedTokEmbedding: fold must be None, True or False, got {fold!r}")
+        if fold is not None and projector is None:
+            raise ValueError(f"MedTokEmbedding: fold={fold!r} without a projector: there is nothing to fold")
+        if projector is not None:
+            if not isinstance(projector, nn.Linear) or projector.in_features != self.embedding_dim:
+                raise ValueError(f"MedTokEmbedding: projector must be an nn.Linear with in_features = S * e_dim = {self.embedding_dim}, got "
+                                 f"{projector!r}")
+            if projector.weight.dtype != torch.float32:
+                raise ValueError(f"MedTokEmbedding: the projector must be fp32 (every product behind the lookup is), got {projector.weight.dtype}")
+            self.projector = projector
+            self.fold = fold
+            self.fold_builds = 0
+            self.__dict__["_fold_cache"] = None           # (key, the normalised-codebook entry it was built from, folded tensors)
 
     @classmethod
     def from_dir(cls, path, quantizer, **kw):
@@ -102,7 +136,16 @@ class MedTokEmbedding(nn.Module):
         [0, num_embeddings)) or the first slot of the table that holds a token id outside its region; validate=False reads nothing
         (such rows are zeros), so the call can be captured in a HIP graph.  out_dtype: torch.float32 / float16 / bfloat16; None =
         fp32, or the autocast dtype where autocast is active.  `out`: a [index.numel(), S * e_dim] device view of that dtype to fill
-        (e.g. a column block of a wider tensor); such a call is not differentiable."""
+        (e.g. a column block of a wider tensor); such a call is not differentiable.
+
+        With a projector the result is projector(embedding) [..., H] (`out`: [index.numel(), H]); padded positions and, with
+        validate=False, positions with a bad index are then the projector's bias row (the projector applied to a row of zeros)."""
+        if getattr(self, "projector", None) is not None:
+            return self._forward_projected(index, padding_mask, validate, out_dtype, out)
+        return self._lookup(index, padding_mask, validate, out_dtype, out)
+
+    def _checked(self, index, padding_mask, out_dtype, out, width):
+        """the argument checks of both forwards -> (padding_mask, out_dtype); `out`, if given, must be [index.numel(), width]"""
         if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
             raise ValueError(f"MedTokEmbedding: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
         if out_dtype is None:
@@ -110,11 +153,17 @@ class MedTokEmbedding(nn.Module):
         if out_dtype not in ops.EMBED_OUT_DTYPES:
             raise ValueError(f"MedTokEmbedding: out_dtype must be one of {ops.EMBED_OUT_DTYPES}, got {out_dtype!r}")
         padding_mask = ops._embed_mask("MedTokEmbedding", padding_mask, index)
+        n = index.numel()
+        if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == out_dtype and tuple(out.shape) == (n, width)):
+            raise ValueError(f"MedTokEmbedding: out must be a {out_dtype} [{n}, {width}] tensor")
+        return padding_mask, out_dtype
+
+    def _lookup(self, index, padding_mask, validate, out_dtype, out):
+        """forward without a projector"""
         q = self.quantizer
         s, e, pad = len(self.types), int(q.e_dim), getattr(q, "_pad", 0)
+        padding_mask, out_dtype = self._checked(index, padding_mask, out_dtype, out, s * e)
         n = index.numel()
-        if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == out_dtype and tuple(out.shape) == (n, s * e)):
-            raise ValueError(f"MedTokEmbedding: out must be a {out_dtype} [{n}, {s * e}] tensor")
         grad_on = out is None and torch.is_grad_enabled()
         want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
         if want_codebook:
@@ -172,3 +221,83 @@ class MedTokEmbedding(nn.Module):
         if at.numel():
             out = out.index_put((at,), self.miss_emb.expand(at.numel(), -1))
         return out.to(out_dtype).reshape(*index.shape, self.embedding_dim)
+
+    # ------------------------------------------------------------------ the projector behind the lookup
+    def fold_table_shape(self):
+        """(rows, columns) of the folded tables: the slots' region sizes summed, H rounded up to 4"""
+        return sum(size for _, size in self._regions()), ops.pad_dim(self.projector.out_features)
+
+    def fold_rule(self, positions: int, cache_valid: bool) -> bool:
+        """fold=None: fold when the projector narrows (H < S * e_dim), the tables fit FOLD_MAX_BYTES and either they are already built
+        for the current weights or positions * S >= FOLD_COLD_FACTOR * rows.
+
+        Measured at 96,000 positions, H = 256, against F.linear(lookup) (profiles/embed_bench.json "project"):
+        at H = S * e_dim = 256 the lookup over warm tables is 0.98x the composition (k rows of H floats per slot are 4x the rows of e_dim
+        floats the plain lookup gathers), so such a projector is not folded; at e_dim = 768 it is 9.4x.  The flop break-even positions *
+        S >= rows (2 * rows * e_dim * H against 2 * positions * S * e_dim * H) did not hold for a call that has to build its tables:
+        0.98x at positions * S = 2.9 rows (cfg 3: the fold takes 1.51 ms, which the call repays at 1.54 us per 100 positions, i.e.
+        from 97,900 positions = 3.0 rows / S), hence the factor; it comes from that one shape and a time taken as linear in the
+        positions.  The module's own unfolded path (small_linear, not F.linear) has not been timed."""
+        rows, hp = self.fold_table_shape()
+        if self.projector.out_features >= self.embedding_dim or rows * hp * 4 > self.FOLD_MAX_BYTES:
+            return False
+        return bool(cache_valid) or positions * len(self.types) >= self.FOLD_COLD_FACTOR * rows
+
+    def _fold_key(self, norm):
+        tensors = (self.projector.weight, self.projector.bias, self.miss_emb)
+        return (id(norm),) + tuple(None if t is None else (t._version, t.data_ptr(), t.device) for t in tensors)
+
+    def _folded(self, norm):
+        """the folded tables of the current weights: (table, row_regions, bias, miss_row), rebuilt only when the key changes"""
+        key = self._fold_key(norm)
+        cache = self._fold_cache
+        if cache is None or cache[0] != key:
+            p, e = self.projector, int(self.quantizer.e_dim)
+            with torch.no_grad():
+                folded = ops.fold_projector(norm[0], self._regions(), p.weight.detach(), None if p.bias is None else p.bias.detach(),
+                                            None if self.miss_emb is None else self.miss_emb.detach().reshape(-1), e_dim=e)
+            self.fold_builds += 1
+            cache = self.__dict__["_fold_cache"] = (key, norm, folded)     # (the entry is kept: its id cannot be handed out again)
+        return cache[2]
+
+    def _forward_projected(self, index, padding_mask, validate, out_dtype, out):
+        """forward with a projector: [..., H].  Folded: one launch over the cached tables (ops.embed_project); else the lookup as it
+        stands, in fp32, followed by the exact fp32 dense product (autograd.small_linear)."""
+        p, q = self.projector, self.quantizer
+        if p.weight.dtype != torch.float32:
+            raise ValueError(f"MedTokEmbedding: the projector must be fp32 (every product behind the lookup is), got {p.weight.dtype}")
+        h, hp, n = p.out_features, ops.pad_dim(p.out_features), index.numel()
+        padding_mask, out_dtype = self._checked(index, padding_mask, out_dtype, out, h)
+        grad_on = out is None and torch.is_grad_enabled()
+        want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
+        norm = None if want_codebook else q._normalised_codebook()
+        fold = False if want_codebook else self.fold
+        if fold is None:
+            cache = self._fold_cache
+            fold = self.fold_rule(n, cache is not None and cache[0] == self._fold_key(norm))
+        if not fold:
+            # the lookup (its own validation, miss-row and codebook gradients), then the dense product; `out` cannot take the fp32 rows
+            with torch.set_grad_enabled(grad_on):                  # (a call that fills `out` is not differentiable: no graph is built)
+                emb = self._lookup(index, padding_mask, validate, torch.float32, None)
+                res = small_linear(emb.reshape(n, self.embedding_dim), p.weight, p.bias).to(out_dtype)
+            if out is not None:
+                out.copy_(res)
+                return out
+            return res.reshape(*index.shape, h)
+        folded = self._folded(norm)
+        regions = self._regions()
+        status = torch.zeros(1, dtype=torch.int32, device=self.tokens.device) if validate else None
+        wants = [t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb)]
+        if grad_on and any(wants):
+            res = _EmbedProjectFunction.apply(p.weight, p.bias, self.miss_emb, index, padding_mask, self.tokens, self.weights, norm[0],
+                                              tuple(regions), int(q.e_dim), folded, out_dtype, status)
+        else:
+            res = ops.embed_project(index, self.tokens, self.weights, *folded[:3], miss_row=folded[3], pad_mask=padding_mask,
+                                    out=out if hp == h else None, out_dtype=out_dtype, status=status)
+        if hp != h:
+            res = res.reshape(n, hp)[:, :h]
+            if out is not None:
+                out.copy_(res)
+        if validate:
+            self._raise_on(int(status.item()), regions)
+        return out if out is not None else res.reshape(*index.shape, h)

@@ -452,6 +452,109 @@ def embed_codes_miss_grad(g_out, index, num_codes, pad_mask=None):
     return g_miss
 
 
+def fold_projector(what, regions, W, b=None, miss=None, e_dim=None):
+    """The consumer's projector applied to the codebook instead of to every position: what embed_project gathers from.
+
+    what [n_codes, d]: the NORMALISED codebook (d % 4 == 0; its first e_dim columns count, default d); regions: per slot (lo, size) in
+    rows of `what`; W fp32 [H, S * e_dim], b fp32 [H] or None: the nn.Linear that follows the lookup; miss fp32 [S * e_dim] (or
+    [1, S * e_dim]) or None.  Returns (table, row_regions, bias, miss_row): table [sum of sizes, Hp] (Hp = H rounded up to 4, the added
+    columns zeros) stacks P_s = what[lo_s : lo_s + size_s] @ W[:, s * e_dim : (s + 1) * e_dim]^T per slot, row_regions [(offset_s,
+    size_s)] says where, bias [Hp], miss_row [Hp] = W @ miss + b (or None).  Every product is small_gemm's exact fp32 chain: 2 * sum of
+    sizes * e_dim * H flops, once per version of the weights."""
+    fn = "fold_projector"
+    if not all(isinstance(t, torch.Tensor) for t in (what, W)) or what.dtype != torch.float32 or W.dtype != torch.float32 or what.dim() != 2 or W.dim() != 2:
+        raise ValueError(f"{fn}: what and W must be fp32 matrices")
+    d = what.shape[1]
+    e = d if e_dim is None else int(e_dim)
+    regions = [(int(lo), int(size)) for lo, size in regions]
+    s = len(regions)
+    if not 1 <= s <= DECODE_MAX_SLOTS or not 1 <= e <= d or d % 4 or W.shape[1] != s * e:
+        raise ValueError(f"{fn}: W must be [H, {s} * {e}] for {s} slots over a [n_codes, {d}] codebook, got {tuple(W.shape)}")
+    for lo, size in regions:
+        if lo < 0 or size < 1 or lo + size > what.shape[0]:
+            raise ValueError(f"{fn}: region [{lo}, +{size}) is not inside the {what.shape[0]} codes")
+    h = W.shape[0]
+    hp = pad_dim(h)
+    if b is not None and (not isinstance(b, torch.Tensor) or b.dtype != torch.float32 or tuple(b.shape) != (h,)):
+        raise ValueError(f"{fn}: b must be fp32 [{h}]")
+    if miss is not None and (not isinstance(miss, torch.Tensor) or miss.dtype != torch.float32 or miss.numel() != s * e):
+        raise ValueError(f"{fn}: miss must be fp32 [{s * e}]")
+    what, W = _dev(what, "what"), _dev(W.detach(), "W")
+    total = sum(size for _, size in regions)
+    if total >= 2 ** 31:
+        raise ValueError(f"{fn}: {total} table rows exceed what one lookup addresses")
+    table = torch.empty((total, hp), dtype=torch.float32, device=what.device)
+    Wp = torch.nn.functional.pad(W, (0, 0, 0, hp - h)) if hp != h else W                     # [Hp, S * e]: zero rows for the added columns
+    row_regions, at = [], 0
+    for i, (lo, size) in enumerate(regions):
+        Ws = Wp[:, i * e:(i + 1) * e]
+        Ws = torch.nn.functional.pad(Ws, (0, d - e)) if d != e else Ws.contiguous()          # (the codebook's padding columns are zeros)
+        small_gemm(what[lo:lo + size], Ws, trans_b=True, out=table[at:at + size])
+        row_regions.append((at, size))
+        at += size
+    bias = torch.zeros(hp, dtype=torch.float32, device=what.device)
+    if b is not None:
+        bias[:h] = _dev(b.detach(), "b")
+    miss_row = None
+    if miss is not None:
+        miss_row = small_gemm(_dev(miss.detach(), "miss").reshape(1, s * e), Wp, trans_b=True).reshape(hp) + bias
+    return table, row_regions, bias, miss_row
+
+
+def embed_project(index, tokens, weights, table, row_regions, bias, miss_row=None, pad_mask=None, out=None, out_dtype=torch.float32,
+                  status=None):
+    """projector(embed_codes(index, ...)) in one launch, without the [positions, slots * d] activation: the lookup over the folded
+    tables of fold_projector -> [*index.shape, Hp].
+
+    index, tokens, weights, pad_mask, out_dtype, status: as embed_codes (slots * k <= 64).  table [rows, Hp], row_regions [(offset,
+    size)] per slot, bias [Hp], miss_row [Hp] or None: what fold_projector returned.  Per column one fp32 chain: bias, then slots
+    ascending, then list order.  Padded positions are the bias row whatever their index holds; index == num_codes gives miss_row; any
+    other index outside [0, num_codes) gives the bias row and sets bit 4 of `status`; a slot with an id outside its region contributes
+    nothing and sets bit s -- nothing is read back here.  `out`: a [index.numel(), Hp] device view of out_dtype with unit column stride."""
+    fn = "embed_project"
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+    if out_dtype not in EMBED_OUT_DTYPES:
+        raise ValueError(f"{fn}: out_dtype must be one of {EMBED_OUT_DTYPES}, got {out_dtype!r}")
+    pad_mask = _embed_mask(fn, pad_mask, index)
+    tokens, weights, row_regions = _decode_shapes(fn, tokens, weights, table, row_regions)
+    num_codes, s, k = tokens.shape
+    if num_codes < 1:
+        raise ValueError(f"{fn}: the token table is empty")
+    if s * k > 64:
+        raise ValueError(f"{fn}: {s} slots of {k} ids are more than the 64 entries per code the kernel takes")
+    hp = table.shape[1]
+    n = index.numel()
+    for name, t in (("bias", bias), ("miss_row", miss_row)):
+        if (t is not None or name == "bias") and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (hp,)):
+            raise ValueError(f"{fn}: {name} must be fp32 [{hp}], got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if out is not None:
+        align = 16 if out_dtype == torch.float32 else 8
+        if not (isinstance(out, torch.Tensor) and out.dtype == out_dtype and tuple(out.shape) == (n, hp) and out.stride(1) == 1
+                and out.stride(0) % 4 == 0 and out.data_ptr() % align == 0):
+            raise ValueError(f"{fn}: out must be a {out_dtype} [{n}, {hp}] view with unit column stride and {align}-byte aligned rows")
+    index = _dev(index, "index", torch.int64)
+    tokens, weights, table, los, sizes = _decode_on_device(tokens, weights, table, row_regions)
+    bias = _dev(bias, "bias")
+    miss_row = None if miss_row is None else _dev(miss_row, "miss_row")
+    pad_mask = _embed_mask_on_device(pad_mask)
+    if out is not None and not out.is_cuda:
+        _dev(out, "out", out_dtype)
+    if status is not None:
+        status = _dev(status, "status", torch.int32)
+    res = torch.empty((n, hp), dtype=out_dtype, device=table.device) if out is None else out
+    stride = res.stride(0) if n else 0
+    lib = _lib.load()
+    with _on(table.device):
+        head = (index.data_ptr(), _ptr(pad_mask), n, tokens.data_ptr(), weights.data_ptr(), num_codes, s, k, table.data_ptr(), table.shape[0], hp,
+                los, sizes, bias.data_ptr(), _ptr(miss_row), res.data_ptr(), stride)
+        if out_dtype == torch.float32:
+            _lib.check(lib.medtok_embed_project_f32(*head, _ptr(status), _stream(table)), "medtok_embed_project_f32")
+        else:
+            _lib.check(lib.medtok_embed_project_f16(*head, int(out_dtype == torch.bfloat16), _ptr(status), _stream(table)), "medtok_embed_project_f16")
+    return res.view(*index.shape, hp) if out is None else out
+
+
 def soft_vq_backward(x, xhat, what, idx, w, g_zq=None, g_xhat=None, g_out=None, g_vq=None, g_commit=None,
                      vq_scale: float = 0.0, commit_scale: float = 0.0, want_gx: bool = True, want_g_code: bool = True):
     """Sparse backward of the soft top-k assignment: (gx [n, d], g_code [n*k, d]).
@@ -535,15 +638,18 @@ def row_dot(a, b):
     return out
 
 
-def small_gemm(A, B, trans_a: bool = False, trans_b: bool = False):
+def small_gemm(A, B, trans_a: bool = False, trans_b: bool = False, out=None):
     """op(A) @ op(B) in exact fp32 (one fmaf chain per entry, k ascending).  A, B: contiguous fp32 matrices; the transposes
-    are strides, nothing is copied."""
+    are strides, nothing is copied.  out: a contiguous fp32 [m, n] device tensor to fill (e.g. a row block of a larger one)."""
     A, B = _dev(A, "A"), _dev(B, "B")
     (m, k), (sam, sak) = ((A.shape[1], A.shape[0]), (1, A.shape[1])) if trans_a else ((A.shape[0], A.shape[1]), (A.shape[1], 1))
     (k2, n), (sbk, sbn) = ((B.shape[1], B.shape[0]), (1, B.shape[1])) if trans_b else ((B.shape[0], B.shape[1]), (B.shape[1], 1))
     if k != k2:
         raise ValueError(f"small_gemm: inner dimensions differ ({k} vs {k2})")
-    C = torch.empty((m, n), dtype=torch.float32, device=A.device)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (m, n)
+                                and out.is_contiguous()):
+        raise ValueError(f"small_gemm: out must be a contiguous fp32 [{m}, {n}] device tensor")
+    C = torch.empty((m, n), dtype=torch.float32, device=A.device) if out is None else out
     with _on(A.device):
         _lib.check(_lib.load().medtok_small_gemm_f32(A.data_ptr(), sam, sak, B.data_ptr(), sbk, sbn, m, n, k, C.data_ptr(), _stream(A)),
                    "medtok_small_gemm_f32")

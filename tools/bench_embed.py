@@ -15,6 +15,16 @@ Per shape:
                              rows (default: all num_codes where they fit into a quarter of the free memory, else as many as do; the
                              indices are folded into them) -- `table_rows` in the result says how many
 
+--project H: the lookup followed by the consumers' nn.Linear(S * e_dim, H) instead (MedTokEmbedding(projector=...)), the same two
+workloads; four cases per shape, compared before anything is timed (1e-5 of the output's scale):
+
+  folded_warm                module(index, padding_mask, validate=False), fold=True, the folded tables cached: one launch
+  folded_cold                the same call with the cached tables dropped before it: the fold (2 * rows * e_dim * H flops) included
+  forward_backward           the folded forward under autograd and its backward (dW, db, d miss_emb) from a fixed upstream gradient
+  composition                what the parent commit offered: F.linear(module(index, padding_mask, validate=False), W, b)
+
+The result goes under the key "project" of --out (the other keys of an existing file are kept).
+
 Discipline (bench_decode.py's): all sides are warmed up at the timed shape, compared before anything is timed, timed with device
 events over samples of >= 50 ms of back-to-back calls that ALTERNATE between the sides, at least 20 samples each; the shader clock
 (ops.ClockProbe) is read over further kernel samples right behind the timed region.  Algorithmic bytes of the kernel = per position
@@ -55,6 +65,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shapes", default="reference,cfg3")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--project", type=int, default=0, metavar="H", help="time the lookup with a folded nn.Linear(S * e_dim, H) instead")
     args = ap.parse_args()
     if args.reps < 20:
         ap.error("--reps must be at least 20")
@@ -81,6 +92,9 @@ def main():
 
     def stats(ms):
         return dict(ms_median=statistics.median(ms), ms_min=min(ms), ms_max=max(ms), ms_mean=statistics.fmean(ms), samples=len(ms))
+
+    if args.project:
+        return project_mode(args, dev, timed, inner_for, stats)
 
     result = {"tool": "tools/bench_embed.py", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
               "num_codes": args.codes, "positions": [args.batch, args.length], "slots": 4, "k": args.k, "padded_fraction": args.padded,
@@ -189,6 +203,99 @@ def main():
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
     print(line)
+
+
+def project_mode(args, dev, timed, inner_for, stats):
+    import torch
+    import torch.nn.functional as F
+    from medtok_amd import MedTokEmbedding, ops
+    from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer
+    h = args.project
+    result = {"tool": "tools/bench_embed.py --project", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
+              "num_codes": args.codes, "positions": [args.batch, args.length], "slots": 4, "k": args.k, "H": h,
+              "padded_fraction": args.padded, "miss_fraction": args.miss, "shapes": {}}
+    for name in args.shapes.split(","):
+        d, n_e = SHAPES[name]["d"], SHAPES[name]["n_e"]
+        k, num_codes, n_pos = args.k, args.codes, args.batch * args.length
+        torch.manual_seed(0)
+        vq = VectorQuantizer(n_e, d, 0.25, 0.0, True, False, [d, d], k=k)
+        with torch.no_grad():
+            vq.codebook.weight.normal_()
+        vq = vq.to(dev).eval()
+        gen = torch.Generator(device=dev).manual_seed(1)
+        sizes = [hi - lo for lo, hi in (vq._region(t) for t in TYPES)]
+        tokens = torch.stack([torch.randint(0, s, (num_codes, k), generator=gen, device=dev) for s in sizes], 1).contiguous()
+        weights = torch.softmax(torch.randn(num_codes, 4, k, generator=gen, device=dev), -1).contiguous()
+        proj = torch.nn.Linear(4 * d, h).to(dev)
+        module = MedTokEmbedding(vq, tokens, weights, projector=proj, fold=True)
+        plain = MedTokEmbedding(vq, tokens, weights)
+        plain.tokens, plain.weights, plain.miss_emb = module.tokens, module.weights, module.miss_emb
+        del tokens, weights
+        index = torch.randint(0, num_codes, (args.batch, args.length), generator=gen, device=dev)
+        u = torch.rand(args.batch, args.length, generator=gen, device=dev)
+        index[u < args.miss] = num_codes
+        mask = u > 1.0 - args.padded
+        index[mask] = 0
+        g_out = torch.randn(args.batch, args.length, h, generator=gen, device=dev)
+        outs = {}
+
+        def folded_warm():
+            with torch.no_grad():
+                outs["folded_warm"] = module(index, padding_mask=mask, validate=False)
+
+        def folded_cold():
+            module.__dict__["_fold_cache"] = None
+            with torch.no_grad():
+                outs["folded_cold"] = module(index, padding_mask=mask, validate=False)
+
+        def forward_backward():
+            module.zero_grad(set_to_none=True)
+            module(index, padding_mask=mask, validate=False).backward(g_out)
+
+        def composition():
+            with torch.no_grad():
+                outs["composition"] = F.linear(plain(index, padding_mask=mask, validate=False), proj.weight, proj.bias)
+
+        sides = {"folded_warm": folded_warm, "folded_cold": folded_cold, "forward_backward": forward_backward, "composition": composition}
+        for _ in range(args.warmup):
+            for fn in sides.values():
+                fn()
+        torch.cuda.synchronize()
+        scale = float(outs["composition"].abs().max())
+        err = float((outs["folded_warm"] - outs["composition"]).abs().max()) / scale
+        if not err <= 1e-5 or not torch.equal(outs["folded_warm"], outs["folded_cold"]):
+            raise SystemExit(f"{name}: folded lookup and composition disagree (rel {err})")
+        inner = {s: inner_for(fn) for s, fn in sides.items()}
+        ms = {s: [] for s in sides}
+        for _ in range(args.reps):                          # the sides alternate
+            for s, fn in sides.items():
+                ms[s].append(timed(fn, inner[s]))
+        with ops.ClockProbe(dev, max_seconds=10.0) as probe:
+            for _ in range(max(2, args.reps // 4)):
+                timed(folded_warm, inner["folded_warm"])
+        clock = probe.result()
+        st = {s: stats(v) for s, v in ms.items()}
+        rows, hp = module.fold_table_shape()
+        live = int((~mask & (index < num_codes)).sum())
+        entry = {"d": d, "n_e": n_e, "k": k, "H": h, "num_codes": num_codes, "positions": n_pos, "live_positions": live,
+                 "table_rows": rows, "table_bytes": rows * hp * 4, "fold_flops": 2 * rows * d * h, "per_position_product_flops": 2 * n_pos * 4 * d * h,
+                 "activation_bytes_not_written": n_pos * 4 * d * 4, "rel_folded_vs_composition": err,
+                 "folded_warm_algorithmic_bytes": live * 4 * 12 * k + n_pos * 9 + n_pos * hp * 4 + rows * hp * 4,
+                 "clock_ghz": clock.get("ghz_mean"), "clock_region": "further folded_warm samples right behind the timed region"}
+        for s in sides:
+            entry[s] = dict(st[s], calls_per_sample=inner[s], positions_per_s=n_pos / (st[s]["ms_median"] * 1e-3))
+        entry["folded_warm_speedup_over_composition"] = st["composition"]["ms_median"] / st["folded_warm"]["ms_median"]
+        entry["folded_cold_speedup_over_composition"] = st["composition"]["ms_median"] / st["folded_cold"]["ms_median"]
+        result["shapes"][name] = entry
+        del module, plain, outs, index, mask, g_out
+        torch.cuda.empty_cache()
+    if args.out:
+        path = Path(args.out)
+        whole = json.loads(path.read_text()) if path.exists() else {}
+        whole["project"] = result
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(whole, indent=1) + "\n")
+    print(json.dumps(result))
 
 
 if __name__ == "__main__":
