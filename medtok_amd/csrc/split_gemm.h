@@ -451,6 +451,10 @@ __global__ __launch_bounds__(G_THREADS, 2) void split_gemm_kernel(const SplitGem
 // iteration are issued before the first conversion).  With seg_len: the rows come in segments of seg_rows (a [B, L, d] batch) of
 // which only the first seg_len[b] are converted -- padding tokens are never read as keys.  (Its 62 registers let one of its waves
 // per SIMD run beside a resident split_gemm_kernel block: issued behind a dense product, the pass starts under it.)
+// (SPLIT_OPAQUE: the scaled value passes through an empty asm statement.  Without it hipcc folds the multiplication into the
+// conversion of a second copy of hi -- v_fma_mixlo_f16 hi', scale, x, 0 -- and takes lo from that copy: (-0) + (+0) = +0, so an element
+// whose scaled value is -0 got hi = -0 from the stored copy but lo = (-0) - (+0) = -0 instead of the +0 of x - fp32(hi).)
+#define SPLIT_OPAQUE(x) asm("" : "+v"(x))
 template <int U>
 __global__ __launch_bounds__(256) void split_half_kernel(const float *__restrict__ src, long n, int d, long src_stride, int dp, float scale,
                                                          _Float16 *__restrict__ hi, _Float16 *__restrict__ lo,
@@ -484,7 +488,8 @@ __global__ __launch_bounds__(256) void split_half_kernel(const float *__restrict
             half8 h, l;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float x = (j < 4 ? va[u][j] : vb[u][j - 4]) * scale;
+                float x = (j < 4 ? va[u][j] : vb[u][j - 4]) * scale;
+                SPLIT_OPAQUE(x);
                 h[j] = (_Float16)x;
                 l[j] = (_Float16)(x - (float)h[j]);
             }
@@ -562,7 +567,8 @@ __global__ __launch_bounds__(256) void split_half_t_kernel(const float *__restri
         half8 hh, ll;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float x = tile[rs + 8 * h8 + j][c] * scale;        // (rows past n were loaded as zeros)
+            float x = tile[rs + 8 * h8 + j][c] * scale;              // (rows past n were loaded as zeros)
+            SPLIT_OPAQUE(x);
             hh[j] = (_Float16)x;
             ll[j] = (_Float16)(x - (float)hh[j]);
         }

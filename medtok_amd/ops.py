@@ -756,8 +756,10 @@ def half_image(x, dp: int, dtype, transpose: bool = False, group_cols: int = 0, 
 
 
 def half_image_pair(x, dp: int, np_: int, dtype, group_cols: int = 0, col_sums: bool = False):
-    """(half_image(x, dp), half_image(x, np_, transpose=True, group_cols)) from ONE pass over x (medtok_half_image_pair_f32); rows that the
-    rows of x do not reach in the transposed image's padding stay unwritten only where half_image(transpose=True) leaves them so too"""
+    """(half_image(x, dp), half_image(x, np_, transpose=True, group_cols)) from ONE pass over x (medtok_half_image_pair_f32), bit for bit.
+    Both images are written completely: columns d .. dp - 1 of the plain image and columns n .. np_ - 1 of the transposed one (whole
+    64-row tiles of padding included) are +0 -- the weight-gradient product multiplies that padding.  col_sums: + the fp32 column sums
+    of x, the sum over the 64-row tiles of the kernel's partials (tests/test_gpu_operand_images.py)"""
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
         raise _lib.MedTokLibraryError("half_image_pair: expected an fp32 [n, d] matrix with contiguous rows on an MI355X device")
     n, d = x.shape
