@@ -289,6 +289,35 @@ int medtok_embed_project_f16(const int64_t *index, const uint8_t *pad, int64_t n
 size_t medtok_embed_codes_miss_grad_workspace_bytes(int64_t n, int width);
 int medtok_embed_codes_miss_grad_f32(const float *g_out, int64_t g_stride, const int64_t *index, const uint8_t *pad, int64_t n,
                                      int64_t num_codes, int width, float *g_miss, void *ws, size_t ws_bytes, void *stream);
+/* Bag pooling: the normalised mean of a bag of codes in one pass (what the reference's QA adapter computes per sample in a Python loop
+ * over the materialised table: gather, L2-normalise each row over its full width, mean over the set; review.py:50-64).  index
+ * [bags, bag_len] int64, pad [bags, bag_len] or NULL (non-zero = padded, any pattern).  With row(p) the slots * d floats
+ * medtok_embed_codes_f32 writes for position p (the same fp32 chain, the same kinds of position, the same status bits):
+ *   out[b] = ( sum over the unpadded p of bag b, in the fixed order given below, of n(row(p)) ) / (float)live_b
+ * n(v) = v / max(|v|_2, 1e-12) over the WHOLE row (normalize != 0; computed as v * (1 / max(sqrt(sum v^2), 1e-12))) or v (normalize == 0);
+ * live_b = the unpadded positions of the bag (a bad index counts, as a row of zeros); live_b == 0 gives a row of zeros (the reference:
+ * NaN); a row of norm 0 contributes zeros.  Padded positions are not read: neither their index nor the tables.  The sum starts from +0
+ * and runs in a fixed order -- per MEDTOK_EMBED_POOL_CHUNK = 16 consecutive positions (positions j, j + 4, .. per wavefront j % 4 in
+ * ascending order, then the four wavefronts in order), then the chunks in order -- without float atomics: the bits depend on (index,
+ * pad, bag_len, the tables) only, and with normalize == 0 a bag with one unpadded position holds that position's row.
+ * slots * topk <= 64, slots * d <= 4096.  out [bags, slots * d] fp32, out_stride in elements (0 = slots * d, a multiple of 4);
+ * counts: int32 [bags, 2] = (live_b, the unpadded miss positions of b), or NULL; ws from the workspace query (host arithmetic: the
+ * chunks' partial sums and counts; where it returns 0 -- no bags, or bag_len == 0 -- ws may be NULL).  One launch holds at most 2^24 - 1
+ * blocks: bags * ceil(bag_len / 16) beyond that is an error, not a split.  Argument conventions and errors as medtok_embed_codes_f32:
+ * nothing traps, nothing is read back.
+ *
+ * medtok_embed_pool_miss_grad_f32: g_acc[width] = sum over the bags in order of (miss_b / live_b) * g_out[b, :] (fp32 [bags, width],
+ * row stride g_stride, 0 = width; counts as written above; bags with live_b == 0 or miss_b == 0 are skipped), per 256 consecutive bags,
+ * then those partial sums in order; no float atomics.  Every miss position carries the same vector, so this is the gradient of the miss
+ * row for normalize == 0, and what medtok_normalize_backward_f32 takes to it otherwise.  ws: medtok_embed_pool_workspace_bytes(bags, 1,
+ * width) suffices. */
+size_t medtok_embed_pool_workspace_bytes(int64_t bags, int64_t bag_len, int width);
+int medtok_embed_pool_f32(const int64_t *index, const uint8_t *pad, int64_t bags, int64_t bag_len, const int64_t *tokens,
+                          const float *weights, int64_t num_codes, int slots, int topk, const float *what, int64_t n_codes, int d,
+                          const int64_t *region_lo, const int64_t *region_size, const float *miss, int normalize, float *out,
+                          int64_t out_stride, int *counts, int *status, void *ws, size_t ws_bytes, void *stream);
+int medtok_embed_pool_miss_grad_f32(const float *g_out, int64_t g_stride, const int *counts, int64_t bags, int width, float *g_acc,
+                                    void *ws, size_t ws_bytes, void *stream);
 
 /* ---- fp32-accurate dense products on the fp16 matrix pipe (the projections around the cross-attention core:
  * nn.MultiheadAttention's in_proj / out_proj and the folded W_k / W_v products, vector_quantization_soft_one_new.py:17-51).

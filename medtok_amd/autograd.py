@@ -558,6 +558,32 @@ class _EmbedCodesFunction(torch.autograd.Function):
         return g_miss, None, None, None, None, None, None, None, None
 
 
+class _EmbedPoolFunction(torch.autograd.Function):
+    """MedTokEmbedding.pooled with a frozen codebook under autograd: the pooling kernels (medtok_embed_pool_f32), whose one
+    differentiable input is the miss row (the table is a constant).  Every unpadded miss position of bag b adds n(miss) / live_b to
+    pooled[b], so backward is G = sum_b (miss_b / live_b) g[b] in bag order (medtok_embed_pool_miss_grad_f32: fixed order, no float
+    atomics, two runs give the same bits) and, with normalisation, G taken through n by ops.normalize_backward."""
+
+    @staticmethod
+    def forward(ctx, miss, index, pad_mask, tokens, weights, what, regions, normalize, status):
+        out, counts = ops.embed_pool(index, tokens, weights, what, regions, miss=miss.detach(), pad_mask=pad_mask, normalize=normalize,
+                                     status=status)
+        ctx.save_for_backward(miss, counts)
+        ctx.normalize = bool(normalize)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        miss, counts = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 9
+        g_acc = ops.embed_pool_miss_grad(g, counts)
+        if ctx.normalize:
+            v = miss.detach().reshape(1, -1).contiguous()
+            g_acc = ops.normalize_backward(g_acc.view(1, -1), torch.nn.functional.normalize(v, dim=-1), v)
+        return (g_acc.reshape(miss.shape),) + (None,) * 8
+
+
 class _SmallLinearFunction(torch.autograd.Function):
     """y = x W^T + b under autograd on the library's exact fp32 product (ops.small_gemm: one fmaf chain per entry, any shape): what
     MedTokEmbedding puts behind the lookup where the projector is not folded into the tables.  dX = dY W, dW = dY^T X, db = the column

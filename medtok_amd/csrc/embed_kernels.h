@@ -239,3 +239,268 @@ __global__ __launch_bounds__(256) void embed_project_kernel(const int64_t *__res
         if (on) embed_store4(dst + i, a);
     }
 }
+
+// Bag pooling: pooled[b] = (sum over the unpadded positions p of bag b of n(row(p))) / live_b, where row(p) is what embed_codes_kernel
+// writes for position p (the same fp32 chain, the same four kinds of position, the same status bits), n(v) = v / max(|v|_2, 1e-12)
+// over the WHOLE row of slots * d elements (normalize != 0) or v itself, and live_b counts the unpadded positions (a bad index counts,
+// as a row of zeros).  What the reference's QA adapter does per sample in a Python loop over the materialised table
+// (MedTok_QA_Tutorial/review.py:50-64); neither the table nor the [positions, width] rows ever exist.
+//
+// embed_pool_partial_kernel: a block of 4 wavefronts owns MEDTOK_EMBED_POOL_CHUNK consecutive positions of one bag (block =
+// bag * chunks + chunk: the grid (chunks of a bag, bags) flattened, so that neither axis meets the 65,535 limit); the chunk is a
+// compile-time constant, so the bits of the result never depend on the device or on a launch heuristic.  Position j of the chunk belongs
+// to wavefront j % 4, and a wavefront takes its positions one at a time, all slots:
+//   * up front, for each of its CHUNK / 4 positions: the mask byte and the index (not read under the mask), then the code's
+//     slots * topk <= 64 ids and weights, entry i in lane i as in embed_project_kernel -- every load of a level is in flight before the
+//     first is used; ids are validated there (ballot), so no index and no id forms an address before it has been checked, and every
+//     product with a code index is 64-bit;
+//   * per position: lane l owns the float4 columns (r * 64 + l) * 4, r < R (R = 1, 4, 12 or 16 covers widths up to 256, 1024, 3072, 4096); a
+//     column's slot varies by lane, so each lane fetches its slot's ids and weights with a per-lane source (every lane of the wavefront
+//     is active at every shuffle: all branches around them are wavefront-uniform), issues the k gathers of the column together and
+//     runs the chain acc = +0; acc = fmaf(w_j, e_j, acc) in list order.  The finished row stays in registers (4 R floats per lane);
+//   * the squared norm: per lane over r ascending, x y z w (fmaf), then an xor butterfly over the wavefront, distances 32, 16 .. 1 (every
+//     lane ends with the same bits); the row is scaled by 1 / max(sqrt(ss), 1e-12) (one correctly rounded division per row, then one
+//     multiply per element; exactly 1 without normalisation) and added to the wavefront's accumulator, positions in ascending order.
+// The four accumulators are then added in wavefront order through ONE LDS row (((w0 + w1) + w2) + w3; width * 4 <= 16 KiB of dynamic
+// LDS) and written as partial[block, width]; the chunk's counts of live and of live-miss positions go to chunk_counts[block, 2].  A
+// chunk without an unpadded position writes zeros and reads neither an index nor a table.  No float atomics anywhere.
+//
+// Row in registers, not in LDS: a per-wavefront LDS row of 4096 floats would be 64 KiB per block (two blocks per CU, no better than the
+// registers allow) and every element would cross LDS twice.  A lane holds the row and the accumulator (8 R registers), eight gathered
+// float4 and their ids and weights (48); lists of more than 8 entries are gathered eight at a time.  gfx950 build, <R, MAXK>: VGPRs /
+// waves per SIMD -- <1, 8> 70 / 7, <1, 16> 73 / 6, <4, 8> 96 / 5, <4, 16> 99 / 4, <12, 8> 161 / 3, <12, 16> 163 / 3, <16, 8> 193 / 2,
+// <16, 16> 195 / 2; no AGPRs, no scratch, no spills; LDS 32 bytes static + 4 bytes per column (at most 16 KiB; never the limit).
+//
+// embed_pool_finish_kernel adds a bag's partial rows in chunk order from +0, divides by (float)live_b (a true division; live_b == 0:
+// zeros) and writes out[bag, :] and counts[bag] = (live_b, miss_b).
+#define MEDTOK_EMBED_POOL_CHUNK 16
+#define MEDTOK_EMBED_POOL_TURNS (MEDTOK_EMBED_POOL_CHUNK / 4)
+#define MEDTOK_EMBED_POOL_MAX_WIDTH 4096
+
+template <int R, int MAXK>
+__global__ __launch_bounds__(256) void embed_pool_partial_kernel(const int64_t *__restrict__ index, const uint8_t *__restrict__ pad, long bag_len,
+                                                                 int chunks, const int64_t *__restrict__ tokens, const float *__restrict__ weights,
+                                                                 long num_codes, int slots, int topk, const float *__restrict__ what, int d,
+                                                                 DecodeRegions reg, const float *__restrict__ miss, int normalize,
+                                                                 float *__restrict__ partial, int *__restrict__ chunk_counts, int *status)
+{
+    extern __shared__ float4 pool_row[];                          // width / 4 float4: the running sum over the wavefronts
+    __shared__ int wave_live[4], wave_miss[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long bag = (long)blockIdx.x / chunks;
+    const int chunk = (int)((long)blockIdx.x - bag * chunks);
+    const int width = slots * d, entries = slots * topk;         // entries <= 64, width <= 256 R (checked on the host)
+    const int eslot = lane / topk;                                // the slot of this lane's entry
+    long lo = reg.lo[0], size = reg.size[0];
+#pragma unroll
+    for (int s = 1; s < MEDTOK_DECODE_MAX_SLOTS; ++s)
+        if (eslot == s) { lo = reg.lo[s]; size = reg.size[s]; }
+    unsigned slot_of = 0;                                         // two bits per r: the slot of this lane's column (r * 64 + lane) * 4
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = (r * 64 + lane) * 4;
+        slot_of |= (unsigned)(i < width ? i / d : 0) << (2 * r);
+    }
+    // level 1 and 2 of every position of this wavefront: mask and index, then the code's entries
+    int kind[MEDTOK_EMBED_POOL_TURNS], rowv[MEDTOK_EMBED_POOL_TURNS], badv[MEDTOK_EMBED_POOL_TURNS];   // kind: 0 padded, 1 code, 2 miss, 3 bad index
+    float wgt[MEDTOK_EMBED_POOL_TURNS];
+    long cv[MEDTOK_EMBED_POOL_TURNS];
+#pragma unroll
+    for (int t = 0; t < MEDTOK_EMBED_POOL_TURNS; ++t) {
+        const long p = (long)chunk * MEDTOK_EMBED_POOL_CHUNK + t * 4 + wave;
+        const bool in = p < bag_len;
+        const long gp = bag * bag_len + (in ? p : 0);
+        const bool padded = !in || (pad && pad[gp] != 0);
+        const long c = padded ? 0 : index[gp];
+        const bool is_code = !padded && c >= 0 && c < num_codes;
+        const bool is_miss = !padded && miss && c == num_codes;
+        kind[t] = __builtin_amdgcn_readfirstlane(padded ? 0 : is_code ? 1 : is_miss ? 2 : 3);   // (the lanes agree: one address each)
+        cv[t] = c;
+    }
+    int live = 0, missed = 0;
+#pragma unroll
+    for (int t = 0; t < MEDTOK_EMBED_POOL_TURNS; ++t) {
+        long id = 0;
+        float wv = 0.f;
+        if (kind[t] == 1 && lane < entries) {
+            const long at = cv[t] * entries + lane;               // 64-bit: 0 <= c < num_codes was checked above
+            id = tokens[at];
+            wv = weights[at];
+        }
+        const bool bad_lane = id < 0 || id >= size;               // (a lane without an entry holds 0: in range, size >= 1)
+        const unsigned long long votes = __ballot(bad_lane);
+        int bad_slots = 0;
+#pragma unroll
+        for (int s = 0; s < MEDTOK_DECODE_MAX_SLOTS; ++s)
+            if (s < slots && ((votes >> (s * topk)) & ((1ull << topk) - 1ull)) != 0ull) bad_slots |= 1 << s;
+        rowv[t] = bad_lane ? 0 : (int)(lo + id);                  // lo + size <= n_codes < 2^31 (checked on the host)
+        wgt[t] = wv;
+        badv[t] = bad_slots;
+        if (lane == 0 && status) {
+            if (kind[t] == 3) atomicOr(status, 1 << MEDTOK_EMBED_BAD_INDEX_BIT);
+            if (bad_slots) atomicOr(status, bad_slots);           // (bad implies a code: only such positions loaded an id)
+        }
+        live += kind[t] != 0;
+        missed += kind[t] == 2;
+    }
+    float4 acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+    for (int t = 0; t < MEDTOK_EMBED_POOL_TURNS; ++t) {
+        int what_kind = 0, row = 0, bad_slots = 0;
+        float wv = 0.f;
+#pragma unroll
+        for (int u = 0; u < MEDTOK_EMBED_POOL_TURNS; ++u)          // (selects on constant indices: the arrays stay in registers)
+            if (u == t) { what_kind = kind[u]; row = rowv[u]; bad_slots = badv[u]; wv = wgt[u]; }
+        if (what_kind != 1 && what_kind != 2) continue;           // padded, or a bad index: a row of zeros adds nothing
+        unsigned slots_now = slot_of;                             // opaque per position: the shuffle sources, masks and column addresses derived
+        int lane_now = lane;                                      // from them are recomputed here, not kept in 12 R registers across the loop
+        int topk_now = topk;
+        asm volatile("" : "+v"(slots_now), "+v"(lane_now), "+s"(topk_now));
+        float4 v[R];
+        float ss = 0.f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            v[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r * 256 >= width) continue;                       // uniform over the wavefront
+            const int i = (r * 64 + lane_now) * 4, slot = (int)(slots_now >> (2 * r)) & 3;
+            const bool on = i < width;
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (what_kind == 1) {
+                const bool mix = on && !(bad_slots >> slot & 1);
+                const float *src = what + (i - slot * d);
+#pragma unroll
+                for (int j0 = 0; j0 < MAXK; j0 += 8) {            // lists of more than 8: eight gathers at a time, the chain goes on
+                    if (j0 >= topk_now) break;                        // uniform
+                    int cj[8];
+                    float wj[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {                 // every lane active; lane-dependent source: the column's slot
+                        const int from = slot * topk_now + (j0 + j < topk_now ? j0 + j : 0);     // (a scalar select: entry 0 stands in)
+                        cj[j] = __shfl(row, from, 64);
+                        wj[j] = __shfl(wv, from, 64);
+                    }
+                    if (mix) {
+                        float4 e[8];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j)               // the gathers of this column: in flight together
+                            if (j0 + j < topk_now) e[j] = ld4(src + (long)cj[j] * d);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j)
+                            if (j0 + j < topk_now) {
+                                a.x = fmaf(wj[j], e[j].x, a.x); a.y = fmaf(wj[j], e[j].y, a.y);
+                                a.z = fmaf(wj[j], e[j].z, a.z); a.w = fmaf(wj[j], e[j].w, a.w);
+                            }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);            // (keeps the next group's gathers behind this group's fmafs: registers)
+                }
+            } else if (on) {
+                a = ld4(miss + i);
+            }
+            v[r] = a;
+            ss = fmaf(a.x, a.x, ss); ss = fmaf(a.y, a.y, ss); ss = fmaf(a.z, a.z, ss); ss = fmaf(a.w, a.w, ss);
+        }
+        float inv = 1.f;
+        if (normalize) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) ss = ss + __shfl_xor(ss, off, 64);
+            inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            acc[r].x = fmaf(v[r].x, inv, acc[r].x); acc[r].y = fmaf(v[r].y, inv, acc[r].y);
+            acc[r].z = fmaf(v[r].z, inv, acc[r].z); acc[r].w = fmaf(v[r].w, inv, acc[r].w);
+        }
+    }
+    if (lane == 0) { wave_live[wave] = live; wave_miss[wave] = missed; }
+    float *dst = partial + (long)blockIdx.x * width;
+#pragma unroll 1
+    for (int w = 0; w < 4; ++w) {                                 // ((w0 + w1) + w2) + w3: a lane meets its own columns only
+        if (wave == w) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int q = r * 64 + lane;
+                if (q * 4 >= width) continue;
+                float4 a = acc[r];
+                if (w > 0) {
+                    const float4 b = pool_row[q];
+                    a.x = b.x + a.x; a.y = b.y + a.y; a.z = b.z + a.z; a.w = b.w + a.w;
+                }
+                if (w < 3) pool_row[q] = a;
+                else st4(dst + q * 4, a);
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        chunk_counts[2 * (long)blockIdx.x] = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
+        chunk_counts[2 * (long)blockIdx.x + 1] = wave_miss[0] + wave_miss[1] + wave_miss[2] + wave_miss[3];
+    }
+}
+
+// grid = (bags, ceil(width / 1024)); a thread owns one float4 column of one bag
+__global__ __launch_bounds__(256) void embed_pool_finish_kernel(const float *__restrict__ partial, const int *__restrict__ chunk_counts, int chunks,
+                                                                int width, float *__restrict__ out, long out_stride, int *__restrict__ counts)
+{
+    __shared__ int bag_live;
+    const long first = (long)blockIdx.x * chunks;                 // the bag's first chunk
+    if (threadIdx.x == 0) {                                       // one thread adds the chunks' counts (integers: any order), the block reads the sum
+        int live_sum = 0, missed = 0;
+        for (int ch = 0; ch < chunks; ++ch) {
+            live_sum += chunk_counts[2 * (first + ch)];
+            missed += chunk_counts[2 * (first + ch) + 1];
+        }
+        bag_live = live_sum;
+        if (counts && blockIdx.y == 0) {
+            counts[2 * (long)blockIdx.x] = live_sum;
+            counts[2 * (long)blockIdx.x + 1] = missed;
+        }
+    }
+    __syncthreads();
+    const int live = bag_live;
+    const int i = (blockIdx.y * 256 + threadIdx.x) * 4;
+    if (i >= width) return;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int ch = 0; ch < chunks; ++ch) {
+        const float4 p = ld4(partial + (first + ch) * width + i);
+        a.x = a.x + p.x; a.y = a.y + p.y; a.z = a.z + p.z; a.w = a.w + p.w;
+    }
+    if (live > 0) {
+        const float n = (float)live;
+        a.x = a.x / n; a.y = a.y / n; a.z = a.z / n; a.w = a.w / n;
+    } else {
+        a = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    st4(out + (long)blockIdx.x * out_stride + i, a);
+}
+
+// Gradient of the miss row through the pool: every unpadded miss position of bag b carries the same vector, so with the upstream g_out
+// [bags, width] the gradient w.r.t. that vector is G[col] = sum over the bags of (miss_b / live_b) * g_out[b, col] -- the whole gradient
+// of the miss row without normalisation, and what the caller takes through the normalisation's backward with it.  Fixed order, no float
+// atomics, the two stages of embed_miss_grad_*: a block owns MEDTOK_EMBED_GRAD_CHUNK consecutive bags and runs acc = fmaf(coef_b, g, acc)
+// over them in bag order (bags with live_b == 0 or miss_b == 0 are skipped) into partial[chunk, col]; embed_miss_grad_sum_kernel then adds
+// the partials in chunk order.  grid = (chunks of bags, ceil(width / 256)); a thread owns one column.
+__global__ __launch_bounds__(256) void embed_pool_miss_grad_partial_kernel(const float *__restrict__ g_out, long g_stride, const int *__restrict__ counts,
+                                                                           long bags, int width, float *__restrict__ partial)
+{
+    __shared__ float coef[MEDTOK_EMBED_GRAD_CHUNK];
+    const int t = threadIdx.x;
+    const long first = (long)blockIdx.x * MEDTOK_EMBED_GRAD_CHUNK, b = first + t;
+    float cf = 0.f;
+    if (b < bags) {
+        const int live = counts[2 * b], missed = counts[2 * b + 1];
+        if (live > 0 && missed > 0) cf = (float)missed / (float)live;
+    }
+    coef[t] = cf;
+    __syncthreads();
+    const int col = blockIdx.y * 256 + t;
+    if (col >= width) return;
+    const int rows = (int)(bags - first < MEDTOK_EMBED_GRAD_CHUNK ? bags - first : MEDTOK_EMBED_GRAD_CHUNK);
+    float acc = 0.f;
+    for (int r = 0; r < rows; ++r) {
+        const float cf_r = coef[r];
+        if (cf_r != 0.f) acc = fmaf(cf_r, g_out[(first + r) * g_stride + col], acc);
+    }
+    partial[(long)blockIdx.x * width + col] = acc;
+}

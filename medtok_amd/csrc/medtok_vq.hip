@@ -1193,6 +1193,85 @@ extern "C" int medtok_embed_codes_miss_grad_f32(const float *g_out, int64_t g_st
     return check_launch("embed_codes_miss_grad");
 }
 
+// ---- bag pooling: the normalised mean of the unpadded positions of each bag (embed_pool_*_kernel)
+static size_t pool_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+extern "C" size_t medtok_embed_pool_workspace_bytes(int64_t bags, int64_t bag_len, int width)
+{
+    if (bags < 0 || bag_len < 0 || width < 1) return 0;
+    const size_t blocks = (size_t)bags * (size_t)((bag_len + MEDTOK_EMBED_POOL_CHUNK - 1) / MEDTOK_EMBED_POOL_CHUNK);
+    // partial sums [bags, chunks, width] fp32, then the chunks' (live, miss) counts [bags, chunks, 2] int32
+    return pool_round(blocks * (size_t)width * sizeof(float)) + pool_round(blocks * 2 * sizeof(int));
+}
+
+extern "C" int medtok_embed_pool_f32(const int64_t *index, const uint8_t *pad, int64_t bags, int64_t bag_len, const int64_t *tokens,
+                                     const float *weights, int64_t num_codes, int slots, int topk, const float *what, int64_t n_codes, int d,
+                                     const int64_t *region_lo, const int64_t *region_size, const float *miss, int normalize, float *out,
+                                     int64_t out_stride, int *counts, int *status, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "embed_pool";
+    DecodeRegions reg;
+    if (bag_len < 0 || bag_len >= (1ll << 31)) return fail("%s: bag_len=%ld unsupported", fn, (long)bag_len);
+    if (int rc = decode_args(fn, bags, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
+    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
+    if (slots * topk > 64) return fail("%s: slots * topk = %d entries per code exceed one wavefront", fn, slots * topk);
+    const int64_t wide = (int64_t)slots * d;
+    if (wide > MEDTOK_EMBED_POOL_MAX_WIDTH) return fail("%s: rows of slots * d = %ld floats exceed %d", fn, (long)wide, MEDTOK_EMBED_POOL_MAX_WIDTH);
+    const int width = (int)wide;
+    if (out_stride == 0) out_stride = width;
+    if (out_stride < width || (out_stride & 3)) return fail("%s: out_stride must be >= slots * d and a multiple of 4", fn);
+    if (bags == 0) return 0;
+    const int64_t chunks = (bag_len + MEDTOK_EMBED_POOL_CHUNK - 1) / MEDTOK_EMBED_POOL_CHUNK;
+    // a launch holds at most 2^32 threads along x: 2^24 - 1 blocks of 256 (one per chunk in the first kernel, one per bag in the second)
+    const int64_t max_blocks = 0xffffffffll / 256;
+    if (bags > max_blocks || (chunks && bags > max_blocks / chunks))
+        return fail("%s: %ld bags x %ld chunks exceed one launch (%ld blocks of 256 threads)", fn, (long)bags, (long)chunks, (long)max_blocks);
+    if (!tokens || !weights || !what || !out || (bag_len > 0 && !index)) return fail("%s: index, tokens, weights, what and out are required", fn);
+    const size_t need = medtok_embed_pool_workspace_bytes(bags, bag_len, width);
+    if (need && (!ws || ws_bytes < need)) return fail("%s: workspace too small (%zu bytes given, %zu needed)", fn, ws_bytes, need);
+    const size_t blocks = (size_t)(bags * chunks);
+    float *partial = (float *)ws;
+    int *chunk_counts = (int *)((char *)ws + pool_round(blocks * (size_t)width * sizeof(float)));
+    hipStream_t s = (hipStream_t)stream;
+#define MEDTOK_POOL_LAUNCH(R, MAXK)                                                                                                        \
+    hipLaunchKernelGGL((embed_pool_partial_kernel<R, MAXK>), dim3((unsigned)blocks), dim3(256), (size_t)width * sizeof(float), s, index, pad, \
+                       (long)bag_len, (int)chunks, tokens, weights, (long)num_codes, slots, topk, what, d, reg, miss, normalize, partial,      \
+                       chunk_counts, status)
+#define MEDTOK_POOL_ROWS(R) do { if (topk <= 8) MEDTOK_POOL_LAUNCH(R, 8); else MEDTOK_POOL_LAUNCH(R, MEDTOK_MAX_TOPK); } while (0)
+    if (blocks) {                                                  // (floats per lane by the row's width: 4, 16, 48 or 64)
+        if (width <= 256) MEDTOK_POOL_ROWS(1);
+        else if (width <= 1024) MEDTOK_POOL_ROWS(4);
+        else if (width <= 3072) MEDTOK_POOL_ROWS(12);
+        else MEDTOK_POOL_ROWS(16);
+    }
+#undef MEDTOK_POOL_ROWS
+#undef MEDTOK_POOL_LAUNCH
+    hipLaunchKernelGGL(embed_pool_finish_kernel, dim3((unsigned)bags, (unsigned)((width + 1023) / 1024)), dim3(256), 0, s, (const float *)partial,
+                       (const int *)chunk_counts, (int)chunks, width, out, (long)out_stride, counts);
+    return check_launch(fn);
+}
+
+extern "C" int medtok_embed_pool_miss_grad_f32(const float *g_out, int64_t g_stride, const int *counts, int64_t bags, int width, float *g_acc,
+                                               void *ws, size_t ws_bytes, void *stream)
+{
+    if (bags < 0 || width < 1) return fail("embed_pool_miss_grad: bad shape bags=%ld width=%d", (long)bags, width);
+    if (g_stride == 0) g_stride = width;
+    if (g_stride < width) return fail("embed_pool_miss_grad: g_stride must be >= width");
+    if (!g_acc) return fail("embed_pool_miss_grad: g_acc is required");
+    if (bags > 0 && (!g_out || !counts)) return fail("embed_pool_miss_grad: g_out and counts are required");
+    const long chunks = (long)((bags + MEDTOK_EMBED_GRAD_CHUNK - 1) / MEDTOK_EMBED_GRAD_CHUNK);
+    if (chunks > 0x7fffffffl) return fail("embed_pool_miss_grad: %ld bags exceed one launch", (long)bags);
+    if (chunks && (!ws || ws_bytes < pool_round((size_t)chunks * (size_t)width * sizeof(float))))
+        return fail("embed_pool_miss_grad: workspace too small (%zu bytes given)", ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned col_blocks = (unsigned)((width + 255) / 256);
+    if (chunks)
+        hipLaunchKernelGGL(embed_pool_miss_grad_partial_kernel, dim3((unsigned)chunks, col_blocks), dim3(256), 0, s, g_out, (long)g_stride, counts,
+                           (long)bags, width, (float *)ws);
+    hipLaunchKernelGGL(embed_miss_grad_sum_kernel, dim3(col_blocks), dim3(256), 0, s, (const float *)ws, chunks, width, g_acc);
+    return check_launch("embed_pool_miss_grad");
+}
+
 // ================================================================= training half: sparse backward, normalize backward, InfoNCE
 #include "train_kernels.h"
 

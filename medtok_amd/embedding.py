@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import _EmbedCodesFunction, _EmbedProjectFunction, small_linear
+from .autograd import _EmbedCodesFunction, _EmbedPoolFunction, _EmbedProjectFunction, small_linear
 
 DEFAULT_TYPES = ("text", "graph", "shared", "shared")
 
@@ -221,6 +221,74 @@ class MedTokEmbedding(nn.Module):
         if at.numel():
             out = out.index_put((at,), self.miss_emb.expand(at.numel(), -1))
         return out.to(out_dtype).reshape(*index.shape, self.embedding_dim)
+
+    # ------------------------------------------------------------------ bag pooling
+    def pooled(self, index, padding_mask=None, normalize: bool = True, validate: bool = True):
+        """index int64 [B, L] -> fp32 [B, S * e_dim]: the mean over each bag's unpadded positions of the L2-normalised rows `forward`
+        would give, in one pass and without the [B, L, S * e_dim] rows (ops.embed_pool).  What the reference's QA adapter computes per
+        sample in a Python loop over embeddings_all.npy (MedTok_QA_Tutorial/review.py:50-64: gather the sample's codes, F.normalize
+        each 256-wide row, mean over the set):
+
+            pooled[b] = (sum over the unpadded p of bag b, in a fixed order, of n(row(p))) / live_b,     n(v) = v / max(|v|_2, 1e-12)
+
+        The norm runs over the whole row (all slots), not per slot; normalize=False: n(v) = v.  padding_mask: bool / uint8 [B, L],
+        True = padded, any pattern (not only a prefix); padded positions are not read.  live_b counts the unpadded positions: a
+        position with a bad index counts (validate=False: as a row of zeros).  Deviation from the reference: a bag without an unpadded
+        position is a row of ZEROS (the reference's mean over an empty set is NaN); a row of norm 0 contributes zeros.  The sum has a
+        fixed order (not strict position order: ops.embed_pool says which) and uses no float atomics: two calls give the same bits, and with normalize=False a bag with one unpadded position
+        holds that position's `forward` row.
+
+        validate=True reads ONE status word back and raises the ValueErrors of `forward` ("code index", or the first slot with a bad
+        id); validate=False reads nothing, so the call can be captured in a HIP graph.  With a frozen codebook the only gradient is
+        miss_emb's (fixed order: two backward runs give the same bits); freeze_codebook=False composes the result from the codebook's
+        own autograd path, F.normalize and a masked mean (off the hot path, as for `forward`).
+
+        With a projector the result is projector(pooled) [B, H] by the exact fp32 dense product on the B pooled rows.  The projector is
+        NOT folded into the tables here: the normalisation sits between the lookup and the projector, and it is not linear."""
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+            raise ValueError(f"MedTokEmbedding: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+        if index.dim() != 2:
+            raise ValueError(f"MedTokEmbedding: pooled takes index [bags, bag_len], got {tuple(index.shape)}")
+        padding_mask = ops._embed_mask("MedTokEmbedding", padding_mask, index)
+        q = self.quantizer
+        s, e, pad = len(self.types), int(q.e_dim), getattr(q, "_pad", 0)
+        grad_on = torch.is_grad_enabled()
+        if grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad:
+            res = self._pooled_composed(index, padding_mask, normalize, validate)
+        else:
+            regions = self._regions()
+            what = q._normalised_codebook()[0]
+            miss = self.miss_emb
+            want_miss = grad_on and miss is not None and miss.requires_grad
+            if miss is not None:
+                if not want_miss:
+                    miss = miss.detach()
+                miss = (torch.nn.functional.pad(miss.view(s, e), (0, pad)) if pad else miss).reshape(-1)
+            status = torch.zeros(1, dtype=torch.int32, device=self.tokens.device) if validate else None
+            if want_miss:
+                res = _EmbedPoolFunction.apply(miss, index, padding_mask, self.tokens, self.weights, what, tuple(regions), bool(normalize), status)
+            else:
+                res = ops.embed_pool(index, self.tokens, self.weights, what, regions, miss=miss, pad_mask=padding_mask, normalize=normalize,
+                                     status=status)[0]
+            if pad:                                               # (the padding columns are zeros: they change no norm)
+                res = res.reshape(-1, s, e + pad)[:, :, :e].reshape(-1, s * e)
+            if validate:
+                self._raise_on(int(status.item()), regions)
+        p = getattr(self, "projector", None)
+        return res if p is None else small_linear(res, p.weight, p.bias)
+
+    def _pooled_composed(self, index, padding_mask, normalize, validate):
+        """freeze_codebook=False: the same function from _forward_composed's rows, torch's normalise and a masked mean, so that
+        codebook.weight gets its gradient (not the hot path)"""
+        rows = self._forward_composed(index, padding_mask, validate, torch.float32)
+        if normalize:
+            rows = torch.nn.functional.normalize(rows, dim=-1)
+        if padding_mask is None:
+            keep = torch.ones(index.shape, dtype=torch.float32, device=rows.device)
+        else:
+            keep = (padding_mask.to(rows.device) == 0).float()
+        live = keep.sum(1, keepdim=True)
+        return torch.where(live > 0, (rows * keep.unsqueeze(-1)).sum(1) / live.clamp(min=1.0), torch.zeros_like(live))
 
     # ------------------------------------------------------------------ the projector behind the lookup
     def fold_table_shape(self):

@@ -452,6 +452,85 @@ def embed_codes_miss_grad(g_out, index, num_codes, pad_mask=None):
     return g_miss
 
 
+EMBED_POOL_CHUNK = 16                       # positions per block of embed_pool_partial_kernel (MEDTOK_EMBED_POOL_CHUNK: part of the result's bits)
+EMBED_POOL_MAX_WIDTH = 4096
+
+
+def embed_pool(index, tokens, weights, what, regions=None, miss=None, pad_mask=None, normalize: bool = True, status=None):
+    """The normalised mean of each bag of code indices, straight from the stored token table -> (pooled fp32 [B, slots * d],
+    counts int32 [B, 2]).
+
+    index int64 [B, L]; tokens, weights, what, regions, miss, status: as embed_codes; pad_mask: bool / uint8 [B, L], True = padded,
+    any pattern.  With row(p) what embed_codes gives for position p,
+        pooled[b] = (sum over the unpadded p of bag b, in a fixed order, of n(row(p))) / live_b,    n(v) = v / max(|v|_2, 1e-12) over the whole row
+    (normalize=False: n(v) = v); live_b counts the unpadded positions (a bad index counts, as a row of zeros); a bag without one is a row
+    of zeros; padded positions are not read.  counts[b] = (live_b, the unpadded miss positions of b): what embed_pool_miss_grad needs.
+    The order is fixed but not strict position order (per EMBED_POOL_CHUNK positions: positions j, j + 4, .. per wavefront j % 4, then the
+    four wavefronts, then the chunks; include/medtok_vq.h) and there are no float atomics: two runs give the same bits, and they depend on
+    (index, pad_mask, L, the tables) only.
+    slots * k <= 64 and slots * d <= EMBED_POOL_MAX_WIDTH.  Nothing is read back here."""
+    fn = "embed_pool"
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+    if index.dim() != 2:
+        raise ValueError(f"{fn}: index must be [bags, bag_len], got {tuple(index.shape)}")
+    pad_mask = _embed_mask(fn, pad_mask, index)
+    tokens, weights, regions = _decode_shapes(fn, tokens, weights, what, regions)
+    num_codes, s, k = tokens.shape
+    if num_codes < 1:
+        raise ValueError(f"{fn}: the token table is empty")
+    d = what.shape[1]
+    width = s * d
+    if s * k > 64 or width > EMBED_POOL_MAX_WIDTH:
+        raise ValueError(f"{fn}: {s} slots x {k} ids (at most 64 entries per code) and rows of {width} floats (at most {EMBED_POOL_MAX_WIDTH}) unsupported")
+    if miss is not None and (not isinstance(miss, torch.Tensor) or miss.dtype != torch.float32 or miss.numel() != width or miss.dim() not in (1, 2)
+                             or miss.shape[-1] != width):
+        raise ValueError(f"{fn}: miss must be fp32 [{width}] or [1, {width}], got {getattr(miss, 'dtype', type(miss))} "
+                         f"{tuple(getattr(miss, 'shape', ()))}")
+    index = _dev(index, "index", torch.int64)
+    tokens, weights, what, los, sizes = _decode_on_device(tokens, weights, what, regions)
+    miss = None if miss is None else _dev(miss, "miss")
+    pad_mask = _embed_mask_on_device(pad_mask)
+    if status is not None:
+        status = _dev(status, "status", torch.int32)
+    bags, bag_len = index.shape
+    pooled = torch.empty((bags, width), dtype=torch.float32, device=what.device)
+    counts = torch.empty((bags, 2), dtype=torch.int32, device=what.device)
+    lib = _lib.load()
+    ws = _ws(lib.medtok_embed_pool_workspace_bytes(bags, bag_len, width), what)
+    with _on(what.device):
+        _lib.check(lib.medtok_embed_pool_f32(index.data_ptr(), _ptr(pad_mask), bags, bag_len, tokens.data_ptr(), weights.data_ptr(), num_codes, s, k,
+                                             what.data_ptr(), what.shape[0], d, los, sizes, _ptr(miss), int(bool(normalize)), pooled.data_ptr(),
+                                             width, counts.data_ptr(), _ptr(status), ws.data_ptr(), ws.numel(), _stream(what)),
+                   "medtok_embed_pool_f32")
+    return pooled, counts
+
+
+def embed_pool_miss_grad(g_out, counts):
+    """What embed_pool's upstream gradient g_out [B, width] sends to the vector every miss position carries: the fp32 [width] sum over
+    the bags of (miss_b / live_b) * g_out[b], counts [B, 2] int32 as embed_pool returned them, added in a fixed order (no float atomics:
+    two runs give the same bits; bags with live_b == 0 or miss_b == 0 are skipped).  With normalize=False this is the gradient of the
+    miss row; otherwise normalize_backward takes it there.  A half-precision g_out is converted to fp32 first."""
+    fn = "embed_pool_miss_grad"
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != 2:
+        raise ValueError(f"{fn}: counts must be an int32 [bags, 2] tensor, got {getattr(counts, 'dtype', type(counts))} "
+                         f"{tuple(getattr(counts, 'shape', ()))}")
+    bags = counts.shape[0]
+    if (not isinstance(g_out, torch.Tensor) or g_out.dtype not in EMBED_OUT_DTYPES or g_out.dim() != 2 or g_out.shape[0] != bags
+            or g_out.shape[1] < 1):
+        raise ValueError(f"{fn}: g_out must be a floating [{bags}, width] tensor, got {tuple(getattr(g_out, 'shape', ()))}")
+    counts = _dev(counts, "counts", torch.int32)
+    width = g_out.shape[1]
+    g_out = _dev(g_out.float(), "g_out")
+    g_acc = torch.empty(width, dtype=torch.float32, device=g_out.device)
+    lib = _lib.load()
+    ws = _ws(lib.medtok_embed_pool_workspace_bytes(bags, 1, width), g_out)
+    with _on(g_out.device):
+        _lib.check(lib.medtok_embed_pool_miss_grad_f32(g_out.data_ptr(), width, counts.data_ptr(), bags, width, g_acc.data_ptr(), ws.data_ptr(),
+                                                       ws.numel(), _stream(g_out)), "medtok_embed_pool_miss_grad_f32")
+    return g_acc
+
+
 def fold_projector(what, regions, W, b=None, miss=None, e_dim=None):
     """The consumer's projector applied to the codebook instead of to every position: what embed_project gathers from.
 

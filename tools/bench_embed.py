@@ -25,6 +25,19 @@ workloads; four cases per shape, compared before anything is timed (1e-5 of the 
 
 The result goes under the key "project" of --out (the other keys of an existing file are kept).
 
+--pool: bag pooling (MedTokEmbedding.pooled: the normalised mean of each bag's unpadded codes, what the reference's QA adapter computes
+per sample, MedTok_QA_Tutorial/review.py:50-64) at two bag shapes per store shape -- the adapter's, 16 bags x 256 left-padded
+positions, and a throughput shape, 4096 bags x 64 -- with --padded of the positions under the mask and --miss at the miss index; three
+cases, compared before anything is timed (1e-5 of the result's scale):
+
+  pooled                     module.pooled(index, padding_mask, validate=False): two launches, [bags, S * e_dim] and the partial sums
+  composition                what the parent commit offered: module(index, padding_mask, validate=False) -> F.normalize -> sum over the
+                             bag / the unmasked count (the padded rows are zeros already); the [bags, L, S * e_dim] rows are written
+  reference_loop             the reference's own loop over the materialised fp32 table: per sample a boolean selection of its codes
+                             (a host read, as its .item()), the gather, F.normalize, mean (table_rows as above)
+
+The result goes under the key "pool" of --out (the other keys are kept).
+
 Discipline (bench_decode.py's): all sides are warmed up at the timed shape, compared before anything is timed, timed with device
 events over samples of >= 50 ms of back-to-back calls that ALTERNATE between the sides, at least 20 samples each; the shader clock
 (ops.ClockProbe) is read over further kernel samples right behind the timed region.  Algorithmic bytes of the kernel = per position
@@ -66,6 +79,7 @@ def main():
     ap.add_argument("--shapes", default="reference,cfg3")
     ap.add_argument("--out", default=None)
     ap.add_argument("--project", type=int, default=0, metavar="H", help="time the lookup with a folded nn.Linear(S * e_dim, H) instead")
+    ap.add_argument("--pool", action="store_true", help="time bag pooling (MedTokEmbedding.pooled) instead")
     args = ap.parse_args()
     if args.reps < 20:
         ap.error("--reps must be at least 20")
@@ -95,6 +109,8 @@ def main():
 
     if args.project:
         return project_mode(args, dev, timed, inner_for, stats)
+    if args.pool:
+        return pool_mode(args, dev, timed, stats)
 
     result = {"tool": "tools/bench_embed.py", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
               "num_codes": args.codes, "positions": [args.batch, args.length], "slots": 4, "k": args.k, "padded_fraction": args.padded,
@@ -293,6 +309,134 @@ def project_mode(args, dev, timed, inner_for, stats):
         path = Path(args.out)
         whole = json.loads(path.read_text()) if path.exists() else {}
         whole["project"] = result
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(whole, indent=1) + "\n")
+    print(json.dumps(result))
+
+
+POOL_BAGS = {"adapter": (16, 256), "throughput": (4096, 64)}
+
+
+def pool_mode(args, dev, timed, stats):
+    import torch
+    import torch.nn.functional as F
+    from medtok_amd import MedTokEmbedding, ops
+    from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer
+    result = {"tool": "tools/bench_embed.py --pool", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
+              "num_codes": args.codes, "slots": 4, "k": args.k, "padded_fraction": args.padded, "miss_fraction": args.miss,
+              "chunk": ops.EMBED_POOL_CHUNK, "samples_of_at_least_ms": 50.0, "shapes": {}}
+
+    def inner_for(fn):                                      # samples of >= 50 ms (aimed at 65): calls of tens of microseconds need
+        inner = 10                                          # thousands, and the first calls are slower than the steady ones, so the
+        for _ in range(6):                                  # count is corrected on samples of its own size until one is long enough
+            sample = timed(fn, inner) * inner
+            if sample >= 60.0 or inner >= 50000:
+                break
+            inner = max(inner + 1, min(50000, math.ceil(inner * 65.0 / max(sample, 1e-3))))
+        return inner
+
+    for name in args.shapes.split(","):
+        d, n_e = SHAPES[name]["d"], SHAPES[name]["n_e"]
+        k, num_codes, width = args.k, args.codes, 4 * d
+        torch.manual_seed(0)
+        vq = VectorQuantizer(n_e, d, 0.25, 0.0, True, False, [d, d], k=k)
+        with torch.no_grad():
+            vq.codebook.weight.normal_()
+        vq = vq.to(dev).eval()
+        gen = torch.Generator(device=dev).manual_seed(1)
+        sizes = [hi - lo for lo, hi in (vq._region(t) for t in TYPES)]
+        tokens = torch.stack([torch.randint(0, s, (num_codes, k), generator=gen, device=dev) for s in sizes], 1).contiguous()
+        weights = torch.softmax(torch.randn(num_codes, 4, k, generator=gen, device=dev), -1).contiguous()
+        module = MedTokEmbedding(vq, tokens, weights).to(dev)
+        del tokens, weights
+        tokens, weights, miss = module.tokens, module.weights, module.miss_emb.detach()
+        free = torch.cuda.mem_get_info(dev)[0]
+        table_rows = min(num_codes, args.table_rows or int(free // 4 // (width * 4)))
+        table = torch.empty(table_rows + 1, width, device=dev)
+        with torch.no_grad():
+            for r0 in range(0, table_rows, 65536):
+                r1 = min(table_rows, r0 + 65536)
+                vq.decode(tokens[r0:r1], weights[r0:r1], out=table[r0:r1], validate=False)
+            table[table_rows] = miss[0]
+        for bag_name, (bags, length) in POOL_BAGS.items():
+            index = torch.randint(0, num_codes, (bags, length), generator=gen, device=dev)
+            index[torch.rand(bags, length, generator=gen, device=dev) < args.miss] = num_codes
+            # left-padded: bag b's first pad_b positions, pad_b uniform in [0, 2 * padded * L) (at most L - 1)
+            pads = (torch.rand(bags, generator=gen, device=dev) * 2 * args.padded * length).long().clamp_(max=length - 1)
+            mask = torch.arange(length, device=dev).expand(bags, length) < pads.view(-1, 1)
+            index[mask] = 0
+            table_index = torch.where(index == num_codes, table_rows, index % table_rows)
+            n_pos, live = bags * length, int((~mask).sum())
+            n_miss = int((~mask & (index == num_codes)).sum())
+            outs = {}
+
+            def pooled():
+                outs["pooled"] = module.pooled(index, padding_mask=mask, validate=False)
+
+            def composition():
+                rows = F.normalize(module(index, padding_mask=mask, validate=False), dim=-1)
+                outs["composition"] = rows.sum(1) / (~mask).sum(1, keepdim=True).clamp(min=1)
+
+            def reference_loop():
+                res = []
+                for b in range(bags):
+                    codes = table_index[b][~mask[b]]
+                    res.append(F.normalize(table[codes], p=2, dim=-1).mean(0))
+                outs["reference_loop"] = torch.stack(res)
+
+            sides = {"pooled": pooled, "composition": composition, "reference_loop": reference_loop}
+            with torch.no_grad():
+                for _ in range(args.warmup):
+                    for fn in sides.values():
+                        fn()
+                torch.cuda.synchronize()
+                scale = float(outs["composition"].abs().max())
+                err = float((outs["pooled"] - outs["composition"]).abs().max()) / scale
+                err_ref = float((outs["pooled"] - outs["reference_loop"]).abs().max()) / scale if table_rows == num_codes else None
+                if not err <= 1e-5 or (err_ref is not None and not err_ref <= 1e-5):
+                    raise SystemExit(f"{name}/{bag_name}: pooled disagrees with the composition ({err}) or the reference loop ({err_ref})")
+                inner = {s: inner_for(fn) for s, fn in sides.items()}
+                ms = {s: [] for s in sides}
+                for _ in range(args.reps):                  # the sides alternate
+                    for s, fn in sides.items():
+                        ms[s].append(timed(fn, inner[s]))
+                with ops.ClockProbe(dev, max_seconds=10.0) as probe:
+                    for _ in range(max(2, args.reps // 4)):
+                        timed(pooled, inner["pooled"])
+                clock = probe.result()
+            st = {s: stats(v) for s, v in ms.items()}
+            chunks = (length + ops.EMBED_POOL_CHUNK - 1) // ops.EMBED_POOL_CHUNK
+            # what the kernels move: per position the index and the mask byte, per live code its ids and weights and k rows of the
+            # codebook per slot (from the caches: n_e * d * 4 bytes are the distinct ones), the partial sums written and read, the result
+            gathered = (live - n_miss) * 4 * k * d * 4
+            entry = {"d": d, "n_e": n_e, "k": k, "bags": bags, "bag_len": length, "positions": n_pos, "live_positions": live,
+                     "miss_positions": n_miss, "table_rows": table_rows, "table_is_complete": table_rows == num_codes,
+                     "rel_pooled_vs_composition": err, "rel_pooled_vs_reference_loop": err_ref,
+                     "bytes_held": {"pooled": bags * width * 4 + int(ops._lib.load().medtok_embed_pool_workspace_bytes(bags, length, width)),
+                                    "pooled_result": bags * width * 4, "pooled_partial_sums_and_counts": bags * chunks * (width * 4 + 8),
+                                    "composition": 2 * n_pos * width * 4 + bags * width * 4,
+                                    "reference_loop_table": (table_rows + 1) * width * 4},
+                     "pooled_traffic_bytes": {"index_and_mask": n_pos * 9, "ids_and_weights": (live - n_miss) * 4 * k * 12,
+                                              "codebook_rows_gathered": gathered, "codebook_distinct": n_e * d * 4,
+                                              "partial_sums_written_and_read": 2 * bags * chunks * width * 4, "result": bags * width * 4},
+                     "composition_traffic_bytes": {"rows_written": n_pos * width * 4, "rows_read_and_normalised_written": 2 * n_pos * width * 4,
+                                                   "normalised_read": n_pos * width * 4},
+                     "clock_ghz": clock.get("ghz_mean"), "clock_ghz_min": clock.get("ghz_min"), "clock_ghz_max": clock.get("ghz_max"),
+                     "clock_region": "further pooled samples right behind the timed region"}
+            for s in sides:
+                entry[s] = dict(st[s], calls_per_sample=inner[s], sample_ms=st[s]["ms_median"] * inner[s], sample_ms_min=st[s]["ms_min"] * inner[s],
+                                positions_per_s=n_pos / (st[s]["ms_median"] * 1e-3))
+            entry["pooled_speedup_over_composition"] = st["composition"]["ms_median"] / st["pooled"]["ms_median"]
+            entry["pooled_speedup_over_reference_loop"] = st["reference_loop"]["ms_median"] / st["pooled"]["ms_median"]
+            entry["pooled_no_slower_than_composition"] = st["pooled"]["ms_median"] <= st["composition"]["ms_median"]
+            result["shapes"][f"{name}/{bag_name}"] = entry
+            del outs, index, mask, table_index
+        del table, module, tokens, weights
+        torch.cuda.empty_cache()
+    if args.out:
+        path = Path(args.out)
+        whole = json.loads(path.read_text()) if path.exists() else {}
+        whole["pool"] = result
         path.parent.mkdir(parents=True, exist_ok=True)
         path.write_text(json.dumps(whole, indent=1) + "\n")
     print(json.dumps(result))
