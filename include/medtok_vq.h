@@ -289,6 +289,27 @@ int medtok_embed_project_f16(const int64_t *index, const uint8_t *pad, int64_t n
 size_t medtok_embed_codes_miss_grad_workspace_bytes(int64_t n, int width);
 int medtok_embed_codes_miss_grad_f32(const float *g_out, int64_t g_stride, const int64_t *index, const uint8_t *pad, int64_t n,
                                      int64_t num_codes, int width, float *g_miss, void *ws, size_t ws_bytes, void *stream);
+/* The gradient of the NORMALISED codebook through the lookup, straight from the upstream gradient of medtok_embed_codes_f32's rows (a
+ * table that follows the tokenizer's codebook during fine-tuning): g_out fp32 [n, slots * d] (row stride g_stride, 0 = slots * d, a
+ * multiple of 4); index, pad, tokens, weights, num_codes, regions as medtok_embed_codes_f32; g_what fp32 [n_codes, d], bins fp32 [n_codes].
+ * Contribution number ct = (p * slots + s) * topk + j is LIVE exactly when the forward mixes that (position, slot): pad[p] == 0,
+ * 0 <= index[p] < num_codes and every one of the topk ids of slot s of that code inside [0, region_size[s]) (one bad id: all topk
+ * contributions of the slot are dead, as the forward writes the block as zeros); miss positions and bad indices contribute nothing.  A
+ * live contribution belongs to row r = region_lo[s] + tokens[index[p], s, j] and carries weights[index[p], s, j] * g_out[p, s * d :
+ * (s + 1) * d].  bins[r] = the row's live contributions; g_what[r] = their sum, exactly zero for a row without any.  Regions may overlap.
+ * The order is fixed and part of the result: a row's contributions in increasing ct, in chunks of MEDTOK_EMBED_CODE_GRAD_CHUNK consecutive
+ * entries of the row's list; a chunk is one fp32 chain per element, acc = +0, acc = fmaf(w, g, acc); a row with one chunk is that chain,
+ * a row with more the sum of its chunk sums in chunk order.  No float atomics: two runs give the same bits.  No [n * slots * topk, d]
+ * buffer of contribution rows is made: the workspace holds the sort (16 bytes per contribution), 12 bytes per codebook row, and at most
+ * ceil(2 * n * slots * topk / CHUNK) chunk sums of d floats -- host arithmetic on (n, slots, topk, n_codes, d); nothing is read back.
+ * n * slots * topk >= 2^31 is an error named as such (the workspace query returns 0 for it), reported before any pointer is looked at
+ * and before anything is launched.  Take g_what to the codebook weight with medtok_normalize_backward_sparse_f32(live = bins). */
+#define MEDTOK_EMBED_CODE_GRAD_CHUNK 256
+size_t medtok_embed_code_grad_workspace_bytes(int64_t n, int slots, int topk, int64_t n_codes, int d);
+int medtok_embed_code_grad_f32(const float *g_out, int64_t g_stride, const int64_t *index, const uint8_t *pad, int64_t n,
+                               const int64_t *tokens, const float *weights, int64_t num_codes, int slots, int topk, int64_t n_codes, int d,
+                               const int64_t *region_lo, const int64_t *region_size, float *g_what, float *bins, void *ws, size_t ws_bytes,
+                               void *stream);
 /* Bag pooling: the normalised mean of a bag of codes in one pass (what the reference's QA adapter computes per sample in a Python loop
  * over the materialised table: gather, L2-normalise each row over its full width, mean over the set; review.py:50-64).  index
  * [bags, bag_len] int64, pad [bags, bag_len] or NULL (non-zero = padded, any pattern).  With row(p) the slots * d floats

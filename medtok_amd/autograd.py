@@ -558,6 +558,38 @@ class _EmbedCodesFunction(torch.autograd.Function):
         return g_miss, None, None, None, None, None, None, None, None
 
 
+class _EmbedCodesTrainFunction(torch.autograd.Function):
+    """MedTokEmbedding.forward with a codebook that trains (freeze_codebook=False): the SAME lookup kernel as the frozen path, so the
+    same rows in every out_dtype, with two differentiable inputs, the codebook weight and the miss row.  Backward, straight from the
+    upstream gradient: ops.embed_codes_code_grad sums w * g per codebook row in a fixed order (medtok_embed_code_grad_f32: a sort of 8
+    bytes per contribution and chunked fmaf chains; no [positions * S * k, d] buffer, no float atomics, nothing read back), then
+    F.normalize's backward exactly as _DecodeFunction finishes (rows no live position selected: bins = 0, zeros), and
+    ops.embed_codes_miss_grad for the miss row.  `what` is the normalised codebook the forward used: a quantizer in train() mode
+    renormalises on every call.  A half-precision upstream gradient is summed in fp32.  Two runs give the same bits."""
+
+    @staticmethod
+    def forward(ctx, weight, miss, index, pad_mask, tokens, weights, what, regions, out_dtype, status):
+        out = ops.embed_codes(index, tokens, weights, what, regions, miss=None if miss is None else miss.detach(), pad_mask=pad_mask,
+                              out_dtype=out_dtype, status=status)
+        ctx.save_for_backward(weight, index, pad_mask, tokens, weights, what)
+        ctx.regions = regions
+        ctx.miss_shape = None if miss is None else miss.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        weight, index, pad_mask, tokens, weights, what = ctx.saved_tensors
+        gw = g_miss = None
+        if g.dtype != torch.float32:
+            g = g.float()                                          # (once, for both sums)
+        if ctx.needs_input_grad[0]:
+            g_what, bins = ops.embed_codes_code_grad(g, index, tokens, weights, what.shape, ctx.regions, pad_mask)
+            gw = ops.normalize_backward(g_what, what, weight.detach(), live=bins)
+        if ctx.miss_shape is not None and ctx.needs_input_grad[1]:
+            g_miss = ops.embed_codes_miss_grad(g, index, tokens.shape[0], pad_mask).reshape(ctx.miss_shape)
+        return (gw, g_miss) + (None,) * 8
+
+
 class _EmbedPoolFunction(torch.autograd.Function):
     """MedTokEmbedding.pooled with a frozen codebook under autograd: the pooling kernels (medtok_embed_pool_f32), whose one
     differentiable input is the miss row (the table is a constant).  Every unpadded miss position of bag b adds n(miss) / live_b to

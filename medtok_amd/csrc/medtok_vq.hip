@@ -10,6 +10,7 @@
 //   assign_kernels.h      soft assignment, fixed-order fp64 sum
 //   decode_kernels.h      (token ids, weights) -> embedding, and its backward
 //   embed_kernels.h       code indices -> stored tokens -> embedding
+//   embed_grad_kernels.h  the codebook's gradient through the lookup: sort keys, chunked per-row sums
 //   train_kernels.h       sparse backward, normalize backward, InfoNCE
 //   loss_kernels.h        alignment / orthogonality losses
 //   attention_*.h         ragged cross-attention cores (fp32, fp16 x 3, LDS-DMA, two-tile, e_dim = 64) and their backward
@@ -2282,6 +2283,109 @@ extern "C" int medtok_ema_stats_f32(const float *zhat, const int64_t *idx, int64
     }
     hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)lmin(4096, (k_codes + 3) / 4)), dim3(256), 0, s, zhat, w.vals[cur], w.offsets, (int)k_codes, d, bins, embed_sum);
     return check_launch("ema_stats");
+}
+
+// ---- the codebook's gradient through the embedding lookup (embed_grad_kernels.h): keys, the sort above, chunked sums
+#include "embed_grad_kernels.h"
+
+struct CodeGradWs {
+    int *counts, *offsets, *first_chunk, *wave_counts, *wave_offsets;
+    uint32_t *keys[2], *vals[2];
+    float *chunk_sums;
+    long extra;                 // Q: the bound on the chunks of rows with several
+    size_t total;
+};
+
+// everything from (contributions, K, d): nothing here depends on the data
+static CodeGradWs code_grad_ws_layout(void *ws, int64_t contributions, int64_t k_codes, int d)
+{
+    CodeGradWs w;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *p = ws ? (char *)ws + off : nullptr; off += align_up(bytes, 256); return (void *)p; };
+    w.counts = (int *)take((size_t)k_codes * 4);                  // the histogram, then (in place) the rows' chunk counts
+    w.offsets = (int *)take((size_t)(k_codes + 1) * 4);
+    w.first_chunk = (int *)take((size_t)(k_codes + 1) * 4);
+    w.wave_counts = (int *)take((size_t)256 * SORT_WAVES * 4);
+    w.wave_offsets = (int *)take(((size_t)256 * SORT_WAVES + 1) * 4);
+    for (int i = 0; i < 2; ++i) { w.keys[i] = (uint32_t *)take((size_t)contributions * 4); w.vals[i] = (uint32_t *)take((size_t)contributions * 4); }
+    w.extra = (long)((2 * contributions + MEDTOK_EMBED_CODE_GRAD_CHUNK - 1) / MEDTOK_EMBED_CODE_GRAD_CHUNK);
+    w.chunk_sums = (float *)take((size_t)w.extra * (size_t)d * sizeof(float));
+    w.total = off;
+    return w;
+}
+
+static bool code_grad_shape_ok(int64_t n, int slots, int topk, int64_t n_codes, int d)
+{
+    return n >= 0 && slots >= 1 && slots <= MEDTOK_DECODE_MAX_SLOTS && topk >= 1 && topk <= MEDTOK_MAX_TOPK && n_codes >= 1 && n_codes < (1ll << 31) &&
+           d > 0 && !(d & 3);
+}
+
+extern "C" size_t medtok_embed_code_grad_workspace_bytes(int64_t n, int slots, int topk, int64_t n_codes, int d)
+{
+    if (!code_grad_shape_ok(n, slots, topk, n_codes, d) || n > ((1ll << 31) - 1) / (slots * topk)) return 0;
+    return code_grad_ws_layout(nullptr, n * slots * topk, n_codes, d).total;
+}
+
+extern "C" int medtok_embed_code_grad_f32(const float *g_out, int64_t g_stride, const int64_t *index, const uint8_t *pad, int64_t n,
+                                          const int64_t *tokens, const float *weights, int64_t num_codes, int slots, int topk, int64_t n_codes,
+                                          int d, const int64_t *region_lo, const int64_t *region_size, float *g_what, float *bins, void *ws,
+                                          size_t ws_bytes, void *stream)
+{
+    const char *fn = "embed_code_grad";
+    if (!code_grad_shape_ok(n, slots, topk, n_codes, d))
+        return fail("%s: bad shape n=%ld slots=%d topk=%d n_codes=%ld d=%d", fn, (long)n, slots, topk, (long)n_codes, d);
+    if (n > ((1ll << 31) - 1) / (slots * topk))
+        return fail("%s: n * slots * topk = %ld x %d x %d contributions reach 2^31 (the sort's payload is 32-bit): split the batch", fn, (long)n,
+                    slots, topk);
+    DecodeRegions reg;
+    if (int rc = decode_args(fn, n, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
+    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
+    if (g_stride == 0) g_stride = (int64_t)slots * d;
+    if (g_stride < (int64_t)slots * d || (g_stride & 3)) return fail("%s: g_stride must be >= slots * d and a multiple of 4", fn);
+    if (!g_what || !bins) return fail("%s: g_what and bins are required", fn);
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        if (hipMemsetAsync(g_what, 0, (size_t)n_codes * d * sizeof(float), s) != hipSuccess || hipMemsetAsync(bins, 0, (size_t)n_codes * sizeof(float), s) != hipSuccess)
+            return fail("%s: memset failed", fn);
+        return 0;
+    }
+    if (!g_out || !index || !tokens || !weights) return fail("%s: g_out, index, tokens and weights are required", fn);
+    const long contributions = (long)n * slots * topk, items = (long)n * slots;
+    CodeGradWs w = code_grad_ws_layout(ws, contributions, n_codes, d);
+    if (!ws || ws_bytes < w.total) return fail("%s: workspace too small (%zu < %zu)", fn, ws_bytes, w.total);
+    hipLaunchKernelGGL(embed_code_grad_zero_kernel, dim3((unsigned)((n_codes + 255) / 256)), dim3(256), 0, s, w.counts, (long)n_codes);
+    const bool narrow = d <= 64;
+    const int per = narrow ? 16 : 4;                              // items per block: 16 or 64 lanes each
+    if (narrow)
+        hipLaunchKernelGGL((embed_code_grad_keys_kernel<16>), dim3((unsigned)((items + per - 1) / per)), dim3(256), 0, s, index, pad, items, tokens,
+                           (long)num_codes, slots, topk, reg, (int)n_codes, w.keys[0], w.vals[0], w.counts);
+    else
+        hipLaunchKernelGGL((embed_code_grad_keys_kernel<64>), dim3((unsigned)((items + per - 1) / per)), dim3(256), 0, s, index, pad, items, tokens,
+                           (long)num_codes, slots, topk, reg, (int)n_codes, w.keys[0], w.vals[0], w.counts);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)n_codes, w.offsets);
+    hipLaunchKernelGGL(embed_code_grad_plan_kernel, dim3((unsigned)((n_codes + 255) / 256)), dim3(256), 0, s, w.counts, (long)n_codes);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)n_codes, w.first_chunk);
+    int cur = 0;
+    for (int shift = 0; shift == 0 || (n_codes >> shift); shift += 8) {       // keys lie in [0, n_codes]: the dead ones sort to the end
+        hipLaunchKernelGGL((radix_count_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], contributions,
+                           (int)n_codes, shift, w.wave_counts);
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.wave_counts, 256 * SORT_WAVES, w.wave_offsets);
+        hipLaunchKernelGGL((radix_scatter_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], w.vals[cur],
+                           contributions, (int)n_codes, shift, w.wave_offsets, w.keys[cur ^ 1], w.vals[cur ^ 1]);
+        cur ^= 1;
+    }
+    const long work = (long)n_codes + w.extra;
+    if (narrow)
+        hipLaunchKernelGGL((embed_code_grad_chunk_kernel<16>), dim3((unsigned)((work + per - 1) / per)), dim3(256), 0, s, g_out, (long)g_stride, index,
+                           weights, (long)num_codes, slots, topk, d, w.vals[cur], w.offsets, w.first_chunk, (long)n_codes, w.extra, bins, g_what,
+                           w.chunk_sums);
+    else
+        hipLaunchKernelGGL((embed_code_grad_chunk_kernel<64>), dim3((unsigned)((work + per - 1) / per)), dim3(256), 0, s, g_out, (long)g_stride, index,
+                           weights, (long)num_codes, slots, topk, d, w.vals[cur], w.offsets, w.first_chunk, (long)n_codes, w.extra, bins, g_what,
+                           w.chunk_sums);
+    hipLaunchKernelGGL(embed_code_grad_combine_kernel, dim3((unsigned)lmin(4096, (n_codes + 3) / 4)), dim3(256), 0, s, w.chunk_sums, w.first_chunk,
+                       (long)n_codes, d, g_what);
+    return check_launch(fn);
 }
 
 extern "C" size_t medtok_code_histogram_workspace_bytes(int64_t k_codes)

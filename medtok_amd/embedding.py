@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import _EmbedCodesFunction, _EmbedPoolFunction, _EmbedProjectFunction, small_linear
+from .autograd import _EmbedCodesFunction, _EmbedCodesTrainFunction, _EmbedPoolFunction, _EmbedProjectFunction, small_linear
 
 DEFAULT_TYPES = ("text", "graph", "shared", "shared")
 
@@ -44,8 +44,10 @@ class MedTokEmbedding(nn.Module):
     codebook's device).  Ids are region-local as every forward returns them; global_ids=True takes rows of codebook.weight and
     subtracts the region offsets once, here.  miss_row: keep `miss_emb`, an nn.Parameter [1, S * e_dim] initialised randn as the
     reference's, served at index num_codes (`miss_index`); without it that index is an error.  freeze_codebook=True (the
-    reference's table is a constant): the only gradient is miss_emb's; False: codebook.weight gets its gradient too, where it
-    requires one (off the hot path: composed from quantizer.decode on the gathered rows).
+    reference's table is a constant): the only gradient is miss_emb's; False: the table follows the codebook and codebook.weight gets
+    its gradient too, where it requires one: the same lookup kernel forward, and backward the per-row sums of the upstream gradient in
+    a fixed order (ops.embed_codes_code_grad: no row-per-contribution buffer, no float atomics, no host read -- with validate=False a
+    fine-tuning step can be captured in a HIP graph like every frozen path).
 
     projector: the nn.Linear(S * e_dim, H) every consumer of the reference puts behind the lookup (`projector(med_code_emb[data.x])`,
     EHRModel_token.py:143,215-217); it becomes a submodule (its parameters train and travel with this module) and forward returns
@@ -166,8 +168,6 @@ class MedTokEmbedding(nn.Module):
         n = index.numel()
         grad_on = out is None and torch.is_grad_enabled()
         want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
-        if want_codebook:
-            return self._forward_composed(index, padding_mask, validate, out_dtype)
         regions = self._regions()
         what = q._normalised_codebook()[0]
         miss = self.miss_emb
@@ -177,7 +177,13 @@ class MedTokEmbedding(nn.Module):
                 miss = miss.detach()
             miss = (torch.nn.functional.pad(miss.view(s, e), (0, pad)) if pad else miss).reshape(-1)
         status = torch.zeros(1, dtype=torch.int32, device=self.tokens.device) if validate else None
-        if want_miss:
+        if want_codebook:
+            # the same kernel and rows; the codebook's gradient comes straight from the upstream gradient (ops.embed_codes_code_grad).  The
+            # columns appended for e_dim % 4 != 0 are handled as VectorQuantizer.decode does: padded here, under autograd
+            wt = q.codebook.weight
+            wp = torch.nn.functional.pad(wt.float(), (0, pad)) if pad else wt.float()
+            res = _EmbedCodesTrainFunction.apply(wp, miss, index, padding_mask, self.tokens, self.weights, what, tuple(regions), out_dtype, status)
+        elif want_miss:
             res = _EmbedCodesFunction.apply(miss, index, padding_mask, self.tokens, self.weights, what, tuple(regions), out_dtype, status)
         else:
             res = ops.embed_codes(index, self.tokens, self.weights, what, regions, miss=miss, pad_mask=padding_mask,
@@ -200,28 +206,6 @@ class MedTokEmbedding(nn.Module):
         raise ValueError(f"MedTokEmbedding: slot {bad} ({self.types[bad]!r}) of the token table holds an id outside [0, {regions[bad][1]}); "
                          f"slots with bad ids: {[i for i in range(len(regions)) if word >> i & 1]}")
 
-    def _forward_composed(self, index, padding_mask, validate, out_dtype):
-        """freeze_codebook=False: the same function with a gradient for codebook.weight, from quantizer.decode's autograd on the
-        gathered rows of the live positions (torch gathers, boolean indexing and a host read: not the hot path)."""
-        padding_mask = ops._embed_mask("MedTokEmbedding", padding_mask, index)
-        flat = index.reshape(-1)
-        if not flat.is_cuda:
-            ops._dev(flat, "index", torch.int64)
-        padded = torch.zeros_like(flat, dtype=torch.bool) if padding_mask is None else padding_mask.reshape(-1).to(flat.device) != 0
-        live = ~padded & (flat >= 0) & (flat < self.num_codes)
-        is_miss = ~padded & (flat == self.num_codes) if self.miss_emb is not None else torch.zeros_like(padded)
-        if validate and bool((~(padded | live | is_miss)).any()):
-            self._raise_on(1 << ops.EMBED_BAD_INDEX_BIT, None)
-        out = torch.zeros(flat.numel(), self.embedding_dim, dtype=torch.float32, device=flat.device)
-        at = live.nonzero().squeeze(1)
-        if at.numel():
-            sel = flat[at]
-            out = out.index_put((at,), self.quantizer.decode(self.tokens[sel], self.weights[sel], types=self.types, validate=validate))
-        at = is_miss.nonzero().squeeze(1)
-        if at.numel():
-            out = out.index_put((at,), self.miss_emb.expand(at.numel(), -1))
-        return out.to(out_dtype).reshape(*index.shape, self.embedding_dim)
-
     # ------------------------------------------------------------------ bag pooling
     def pooled(self, index, padding_mask=None, normalize: bool = True, validate: bool = True):
         """index int64 [B, L] -> fp32 [B, S * e_dim]: the mean over each bag's unpadded positions of the L2-normalised rows `forward`
@@ -240,8 +224,8 @@ class MedTokEmbedding(nn.Module):
 
         validate=True reads ONE status word back and raises the ValueErrors of `forward` ("code index", or the first slot with a bad
         id); validate=False reads nothing, so the call can be captured in a HIP graph.  With a frozen codebook the only gradient is
-        miss_emb's (fixed order: two backward runs give the same bits); freeze_codebook=False composes the result from the codebook's
-        own autograd path, F.normalize and a masked mean (off the hot path, as for `forward`).
+        miss_emb's (fixed order: two backward runs give the same bits); freeze_codebook=False composes the result from `forward`'s rows
+        (the lookup kernel and its codebook gradient), F.normalize and a masked mean: the [B, L, S * e_dim] rows exist on that route.
 
         With a projector the result is projector(pooled) [B, H] by the exact fp32 dense product on the B pooled rows.  The projector is
         NOT folded into the tables here: the normalisation sits between the lookup and the projector, and it is not linear."""
@@ -278,9 +262,9 @@ class MedTokEmbedding(nn.Module):
         return res if p is None else small_linear(res, p.weight, p.bias)
 
     def _pooled_composed(self, index, padding_mask, normalize, validate):
-        """freeze_codebook=False: the same function from _forward_composed's rows, torch's normalise and a masked mean, so that
-        codebook.weight gets its gradient (not the hot path)"""
-        rows = self._forward_composed(index, padding_mask, validate, torch.float32)
+        """freeze_codebook=False: the same function from the lookup's rows (_lookup: the kernel forward, ops.embed_codes_code_grad
+        backward), torch's normalise and a masked mean, so that codebook.weight gets its gradient"""
+        rows = self._lookup(index, padding_mask, validate, torch.float32, None)
         if normalize:
             rows = torch.nn.functional.normalize(rows, dim=-1)
         if padding_mask is None:

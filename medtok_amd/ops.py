@@ -452,6 +452,66 @@ def embed_codes_miss_grad(g_out, index, num_codes, pad_mask=None):
     return g_miss
 
 
+EMBED_CODE_GRAD_CHUNK = 256                 # contributions per fmaf chain of embed_codes_code_grad (MEDTOK_EMBED_CODE_GRAD_CHUNK: part of the bits)
+
+
+def embed_codes_code_grad(g_out, index, tokens, weights, what_shape_or_what, regions=None, pad_mask=None):
+    """Gradient of embed_codes w.r.t. the NORMALISED codebook, straight from the upstream gradient -> (g_what [n_codes, d], bins [n_codes]).
+
+    g_out [*index.shape, slots * d] (a half-precision one is converted to fp32 first); index, tokens, weights, regions, pad_mask as
+    embed_codes; what_shape_or_what: the normalised codebook or its shape (n_codes, d) -- its values are not read.  Contribution
+    (p, s, j) is live exactly when the forward mixes that (position, slot): not padded, 0 <= index[p] < num_codes, every id of the
+    slot inside its region.  It adds weights[index[p], s, j] * g_out[p, s * d : (s + 1) * d] to row lo_s + tokens[index[p], s, j];
+    bins counts a row's live contributions, a row without any is exactly zero.  The order is fixed (a row's contributions by
+    increasing (p, s, j), one fmaf chain from +0 per EMBED_CODE_GRAD_CHUNK of them, the chunk sums added in order; no float atomics):
+    two calls give the same bits.  No [n * slots * k, d] buffer is made and nothing is read back.
+    `normalize_backward(g_what, what, weight, live=bins)` takes the result to the codebook weight."""
+    fn = "embed_codes_code_grad"
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+    pad_mask = _embed_mask(fn, pad_mask, index)
+    if isinstance(what_shape_or_what, torch.Tensor):
+        what = what_shape_or_what
+    else:
+        shape = tuple(int(v) for v in what_shape_or_what)
+        if len(shape) != 2 or min(shape) < 1:
+            raise ValueError(f"{fn}: the codebook's shape must be (n_codes, d), got {shape}")
+        what = torch.empty(shape, dtype=torch.float32, device="meta")          # (shape checks only: no storage)
+    tokens, weights, regions = _decode_shapes(fn, tokens, weights, what, regions)
+    num_codes, s, k = tokens.shape
+    if num_codes < 1:
+        raise ValueError(f"{fn}: the token table is empty")
+    n_codes, d = what.shape
+    n, width = index.numel(), s * d
+    if (not isinstance(g_out, torch.Tensor) or g_out.dtype not in EMBED_OUT_DTYPES or g_out.dim() < 1 or g_out.shape[-1] != width
+            or g_out.numel() != n * width):
+        raise ValueError(f"{fn}: g_out must be a floating [*{tuple(index.shape)}, {width}] tensor, got {getattr(g_out, 'dtype', type(g_out))} "
+                         f"{tuple(getattr(g_out, 'shape', ()))}")
+    if n * s * k >= 1 << 31:
+        raise ValueError(f"{fn}: {n} positions x {s} slots x {k} ids reach 2^31 contributions (the sort's payload is 32-bit): split the batch")
+    index = _dev(index, "index", torch.int64)
+    tokens, weights = _dev(tokens, "tokens", torch.int64), _dev(weights, "weights")
+    pad_mask = _embed_mask_on_device(pad_mask)
+    if not g_out.is_cuda:
+        _dev(g_out, "g_out", g_out.dtype)
+    g_out = g_out.reshape(n, width).float()
+    if n and not (g_out.stride(1) == 1 and g_out.stride(0) >= width and g_out.stride(0) % 4 == 0 and g_out.data_ptr() % 16 == 0):
+        g_out = g_out.contiguous()
+    import ctypes as C
+    arr = C.c_int64 * s
+    los, sizes = arr(*[r[0] for r in regions]), arr(*[r[1] for r in regions])
+    lib = _lib.load()
+    dev = g_out.device
+    g_what = torch.empty((n_codes, d), dtype=torch.float32, device=dev)
+    bins = torch.empty(n_codes, dtype=torch.float32, device=dev)
+    ws = _ws(lib.medtok_embed_code_grad_workspace_bytes(n, s, k, n_codes, d), g_out)
+    with _on(dev):
+        _lib.check(lib.medtok_embed_code_grad_f32(g_out.data_ptr(), g_out.stride(0) if n else 0, index.data_ptr(), _ptr(pad_mask), n, tokens.data_ptr(),
+                                                  weights.data_ptr(), num_codes, s, k, n_codes, d, los, sizes, g_what.data_ptr(), bins.data_ptr(),
+                                                  ws.data_ptr(), ws.numel(), _stream(g_out)), "medtok_embed_code_grad_f32")
+    return g_what, bins
+
+
 EMBED_POOL_CHUNK = 16                       # positions per block of embed_pool_partial_kernel (MEDTOK_EMBED_POOL_CHUNK: part of the result's bits)
 EMBED_POOL_MAX_WIDTH = 4096
 

@@ -38,6 +38,22 @@ cases, compared before anything is timed (1e-5 of the result's scale):
 
 The result goes under the key "pool" of --out (the other keys are kept).
 
+--codebook-grad: forward + backward with freeze_codebook=False (the table follows the tokenizer's codebook during fine-tuning) from a
+fixed upstream gradient, at the same two workloads and in a "hot" variant of each with half the live positions on ONE code (real code
+frequencies are heavy-tailed); the gradients of codebook.weight are compared before anything is timed (1e-5 of their scale):
+
+  kernel                     module(index, padding_mask, validate=False).backward(g): the lookup kernel, then the per-row sums straight
+                             from the upstream gradient (ops.embed_codes_code_grad: sort of 8 bytes per contribution, chunked chains)
+  parent_composition         what the parent commit ran, restated here: boolean selections and nonzero() (host reads), quantizer.decode
+                             on the gathered rows of the live positions, index_put; its backward writes one [d] row per (position, slot,
+                             j) and sorts and sums those
+  torch_table                torch autograd over the materialised table: (weights * F.normalize(W)[tokens + lo]).sum -> table[index]; the
+                             table has --table-rows rows (default 20000: the [rows, S, k, d] gather is 1.2 GB at cfg 3, 37 GB for all 600,000) and the
+                             indices are folded into them
+
+Per case also `peak_bytes`: the rise of torch.cuda.max_memory_allocated() over one forward + backward.  The result goes under the key
+"codebook_grad" of --out (the other keys are kept).
+
 Discipline (bench_decode.py's): all sides are warmed up at the timed shape, compared before anything is timed, timed with device
 events over samples of >= 50 ms of back-to-back calls that ALTERNATE between the sides, at least 20 samples each; the shader clock
 (ops.ClockProbe) is read over further kernel samples right behind the timed region.  Algorithmic bytes of the kernel = per position
@@ -80,6 +96,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--project", type=int, default=0, metavar="H", help="time the lookup with a folded nn.Linear(S * e_dim, H) instead")
     ap.add_argument("--pool", action="store_true", help="time bag pooling (MedTokEmbedding.pooled) instead")
+    ap.add_argument("--codebook-grad", action="store_true", help="time forward + backward with freeze_codebook=False instead")
     args = ap.parse_args()
     if args.reps < 20:
         ap.error("--reps must be at least 20")
@@ -111,6 +128,8 @@ def main():
         return project_mode(args, dev, timed, inner_for, stats)
     if args.pool:
         return pool_mode(args, dev, timed, stats)
+    if args.codebook_grad:
+        return codebook_grad_mode(args, dev, timed, inner_for, stats)
 
     result = {"tool": "tools/bench_embed.py", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
               "num_codes": args.codes, "positions": [args.batch, args.length], "slots": 4, "k": args.k, "padded_fraction": args.padded,
@@ -437,6 +456,120 @@ def pool_mode(args, dev, timed, stats):
         path = Path(args.out)
         whole = json.loads(path.read_text()) if path.exists() else {}
         whole["pool"] = result
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(whole, indent=1) + "\n")
+    print(json.dumps(result))
+
+
+def codebook_grad_mode(args, dev, timed, inner_for, stats):
+    import torch
+    import torch.nn.functional as F
+    from medtok_amd import MedTokEmbedding, ops
+    from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer
+    result = {"tool": "tools/bench_embed.py --codebook-grad", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
+              "num_codes": args.codes, "positions": [args.batch, args.length], "slots": 4, "k": args.k, "padded_fraction": args.padded,
+              "miss_fraction": args.miss, "chunk": ops.EMBED_CODE_GRAD_CHUNK, "shapes": {}}
+    for name in args.shapes.split(","):
+        d, n_e = SHAPES[name]["d"], SHAPES[name]["n_e"]
+        k, num_codes, n_pos, width = args.k, args.codes, args.batch * args.length, 4 * SHAPES[name]["d"]
+        torch.manual_seed(0)
+        vq = VectorQuantizer(n_e, d, 0.25, 0.0, True, False, [d, d], k=k)
+        with torch.no_grad():
+            vq.codebook.weight.normal_()
+        vq = vq.to(dev).eval()
+        gen = torch.Generator(device=dev).manual_seed(1)
+        regions = [vq._region(t) for t in TYPES]
+        tokens = torch.stack([torch.randint(0, hi - lo, (num_codes, k), generator=gen, device=dev) for lo, hi in regions], 1).contiguous()
+        weights = torch.softmax(torch.randn(num_codes, 4, k, generator=gen, device=dev), -1).contiguous()
+        module = MedTokEmbedding(vq, tokens, weights, freeze_codebook=False)
+        del tokens, weights
+        tokens, weights, W, miss = module.tokens, module.weights, vq.codebook.weight, module.miss_emb
+        table_rows = min(num_codes, args.table_rows or 20000)
+        lo = torch.tensor([r[0] for r in regions], device=dev).view(1, -1, 1)
+        g_out = torch.randn(args.batch, args.length, width, generator=gen, device=dev)
+        for variant in ("random", "hot"):
+            index = torch.randint(0, num_codes, (args.batch, args.length), generator=gen, device=dev)
+            u = torch.rand(args.batch, args.length, generator=gen, device=dev)
+            if variant == "hot":                                # half the live positions on one code
+                index[torch.rand(args.batch, args.length, generator=gen, device=dev) < 0.5] = 7
+            index[u < args.miss] = num_codes
+            mask = u > 1.0 - args.padded
+            index[mask] = 0
+            table_index = torch.where(index == num_codes, table_rows, index % table_rows)
+            grads = {}
+
+            def finish(case, out):
+                W.grad = miss.grad = None
+                out.backward(g_out)
+                grads[case] = W.grad
+
+            def kernel():
+                finish("kernel", module(index, padding_mask=mask, validate=False))
+
+            def parent_composition():
+                flat = index.reshape(-1)
+                padded = mask.reshape(-1)
+                live = ~padded & (flat >= 0) & (flat < num_codes)
+                is_miss = ~padded & (flat == num_codes)
+                out = torch.zeros(n_pos, width, dtype=torch.float32, device=dev)
+                at = live.nonzero().squeeze(1)
+                if at.numel():
+                    sel = flat[at]
+                    out = out.index_put((at,), vq.decode(tokens[sel], weights[sel], types=TYPES, validate=False))
+                at = is_miss.nonzero().squeeze(1)
+                if at.numel():
+                    out = out.index_put((at,), miss.expand(at.numel(), -1))
+                finish("parent_composition", out.reshape(args.batch, args.length, width))
+
+            def torch_table():
+                table = (weights[:table_rows].unsqueeze(-1) * F.normalize(W, dim=-1)[tokens[:table_rows] + lo]).sum(2).reshape(table_rows, width)
+                out = torch.cat([table, miss], 0)[table_index] * (~mask).unsqueeze(-1)
+                finish("torch_table", out)
+
+            sides = {"kernel": kernel, "parent_composition": parent_composition, "torch_table": torch_table}
+            peak = {}
+            for _ in range(args.warmup):
+                for s, fn in sides.items():
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    before = torch.cuda.memory_allocated()
+                    fn()
+                    torch.cuda.synchronize()
+                    peak[s] = torch.cuda.max_memory_allocated() - before
+            scale = float(grads["parent_composition"].abs().max())
+            err = float((grads["kernel"] - grads["parent_composition"]).abs().max()) / scale
+            if not err <= 1e-5:
+                raise SystemExit(f"{name}/{variant}: the kernel's codebook gradient and the parent composition's disagree (rel {err})")
+            inner = {s: inner_for(fn) for s, fn in sides.items()}
+            ms = {s: [] for s in sides}
+            for _ in range(args.reps):                          # the sides alternate
+                for s, fn in sides.items():
+                    ms[s].append(timed(fn, inner[s]))
+            with ops.ClockProbe(dev, max_seconds=10.0) as probe:
+                for _ in range(max(2, args.reps // 4)):
+                    timed(kernel, inner["kernel"])
+            clock = probe.result()
+            st = {s: stats(v) for s, v in ms.items()}
+            live = int((~mask & (index < num_codes)).sum())
+            entry = {"d": d, "n_e": n_e, "k": k, "num_codes": num_codes, "positions": n_pos, "live_positions": live, "table_rows": table_rows,
+                     "contribution_rows_bytes": live * 4 * k * d * 4, "codebook_bytes": n_e * d * 4, "rel_kernel_vs_parent_composition": err,
+                     "clock_ghz": clock.get("ghz_mean"), "clock_region": "further kernel samples right behind the timed region"}
+            for s in sides:
+                entry[s] = dict(st[s], calls_per_sample=inner[s], peak_bytes=peak[s], positions_per_s=n_pos / (st[s]["ms_median"] * 1e-3))
+            entry["kernel_speedup_over_parent_composition"] = st["parent_composition"]["ms_median"] / st["kernel"]["ms_median"]
+            entry["kernel_speedup_over_torch_table"] = st["torch_table"]["ms_median"] / st["kernel"]["ms_median"]
+            entry["kernel_no_slower_than_parent_composition"] = st["kernel"]["ms_median"] <= st["parent_composition"]["ms_median"]
+            entry["kernel_peak_smaller_than_parent_composition"] = peak["kernel"] < peak["parent_composition"]
+            result["shapes"][f"{name}/{variant}"] = entry
+            W.grad = miss.grad = None
+            del grads, index, mask, table_index
+            torch.cuda.empty_cache()
+        del module, tokens, weights, g_out
+        torch.cuda.empty_cache()
+    if args.out:
+        path = Path(args.out)
+        whole = json.loads(path.read_text()) if path.exists() else {}
+        whole["codebook_grad"] = result
         path.parent.mkdir(parents=True, exist_ok=True)
         path.write_text(json.dumps(whole, indent=1) + "\n")
     print(json.dumps(result))
