@@ -392,6 +392,19 @@ static int att_keep(uint32_t seed, int64_t qrow, int key, uint32_t thresh)
     return h >= thresh;
 }
 
+/* The mask on its own, for references that restate the attention arithmetic elsewhere (tests/attention_half_reference.py):
+ * mask[r][j] = 1 where the entry of packed query row first_row + r and key j of its code is kept, with the threshold taken from
+ * dropout_p exactly as oracle_shared_kv_attention_train_f32 takes it (dropout_p = 0: everything kept). */
+int oracle_att_keep_mask(uint32_t seed, int64_t first_row, int64_t rows, int64_t keys, float dropout_p, uint8_t *mask)
+{
+    if (rows < 0 || keys < 0 || !(dropout_p >= 0.f && dropout_p < 1.f) || (rows > 0 && keys > 0 && !mask)) return 1;
+    double t = (double)dropout_p * 4294967296.0;
+    const uint32_t thresh = dropout_p > 0.f ? (uint32_t)(t > 4294967295.0 ? 4294967295.0 : t) : 0u;
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t j = 0; j < keys; ++j) mask[r * keys + j] = (uint8_t)(!thresh || att_keep(seed, first_row + r, (int)j, thresh));
+    return 0;
+}
+
 /* Training-mode attention core and its backward (nn.MultiheadAttention with dropout on the attention weights, reference :21,30,45,
  * after the projections are folded into the queries): per code
  *   P = softmax(scale Q KV^T), M = keep / (1 - p), O = (P o M) KV, lse = log sum exp(scale Q KV^T);

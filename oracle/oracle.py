@@ -190,6 +190,16 @@ def shared_kv_attention_train(q, q_start, q_len, kv, kv_start, kv_len, scale, dr
     return (out, lse) if d_out is None else (out, lse, dq, dkv)
 
 
+def att_keep_mask(seed, first_row, rows, keys, dropout_p):
+    """[rows, keys] bool: the dropout mask shared_kv_attention_train applies to packed query rows first_row .. + rows - 1 of a code
+    with `keys` keys (the stateless hash of (seed, packed query row, key of the code); all True for dropout_p = 0)."""
+    mask = np.zeros((int(rows), int(keys)), np.uint8)
+    rc = lib().oracle_att_keep_mask(C.c_uint32(int(seed) & 0xFFFFFFFF), C.c_int64(int(first_row)), C.c_int64(int(rows)), C.c_int64(int(keys)),
+                                    C.c_float(dropout_p), mask.ctypes.data_as(C.POINTER(C.c_uint8)))
+    assert rc == 0
+    return mask.astype(bool)
+
+
 def row_dot(a, b):
     """<a[r], b[r]> per row (the summand of alignment_loss, loss.py:63)."""
     a, ap = _f(a); b, bp = _f(b)
