@@ -339,6 +339,64 @@ int medtok_embed_pool_f32(const int64_t *index, const uint8_t *pad, int64_t bags
                           int64_t out_stride, int *counts, int *status, void *ws, size_t ws_bytes, void *stream);
 int medtok_embed_pool_miss_grad_f32(const float *g_out, int64_t g_stride, const int *counts, int64_t bags, int width, float *g_acc,
                                     void *ws, size_t ws_bytes, void *stream);
+/* The consumer's input sequence in the lookup's launch: what the EHR model builds between `projector(med_code_emb[index])` and its first
+ * transformer layer (EHRModel_token.py:220-232, PositionalEncoding.forward :65-78): a positional row per position, two time rows per
+ * position carried from the position's visit, and the (cls, gender, ethnicity) rows in front.  index, pad [batch, len]; out
+ * [batch, n_prefix + len, hp]; everything up to miss_row is medtok_embed_project_f32's, with n = batch * len.  Row (b, r) of out:
+ *   r < n_prefix                         a copy of prefix[b, r, :]   (prefix fp32 [batch, n_prefix, hp])
+ *   p = r - n_prefix, pad[b, p] != 0     the row r0 medtok_embed_project_f32 writes for the position (the bias row); nothing is added, and
+ *                                        neither index[b, p] nor segment_id[b, p] is read
+ *   otherwise                            ((r0 + position_rows[p]) + segment_rows0[b, g]) + segment_rows1[b, g],   g = segment_id[b, p]
+ * plain fp32 additions in that order, continuing from the fp32 value of the lookup's chain (a miss position and a bad code index take
+ * them like any unpadded position).  position_rows fp32 [n_position_rows >= len, hp]; segment_id int64 [batch, len]; segment_rows0 / 1
+ * fp32 [batch, n_segments, hp], 1 <= n_segments <= MEDTOK_EMBED_SEQ_MAX_SEGMENTS.  Each part may be NULL (segment_id and segment_rows0
+ * come together; segment_rows1 only with segment_rows0; n_prefix = 0 needs no prefix): an absent part adds nothing.  A g outside
+ * [0, n_segments) contributes no segment term and sets bit MEDTOK_EMBED_BAD_SEGMENT_BIT of *status; no address is formed from an
+ * unchecked id.  batch * (n_prefix + len) >= 2^31 is an error named as such, reported before anything is launched.  The _f16 sibling
+ * rounds each finished fp32 value once (bf16 != 0: bf16).  Nothing traps and nothing is read back.
+ *
+ * medtok_embed_sequence_rows_*: the same rows from dense fp32 rows [batch * len, width] in place of the tables (r0 = rows[b * len + p]),
+ * for lookups that do not run over folded tables; any width >= 1, every tensor with row stride = width, out [batch, n_prefix + len, width]. */
+#define MEDTOK_EMBED_BAD_SEGMENT_BIT 5
+#define MEDTOK_EMBED_SEQ_MAX_TERMS 2
+#define MEDTOK_EMBED_SEQ_MAX_SEGMENTS 4096
+int medtok_embed_sequence_f32(const int64_t *index, const uint8_t *pad, int64_t batch, int64_t len, const int64_t *tokens,
+                              const float *weights, int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp,
+                              const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row,
+                              const float *position_rows, int64_t n_position_rows, const int64_t *segment_id,
+                              const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
+                              int64_t n_prefix, float *out, int64_t out_stride, int *status, void *stream);
+int medtok_embed_sequence_f16(const int64_t *index, const uint8_t *pad, int64_t batch, int64_t len, const int64_t *tokens,
+                              const float *weights, int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp,
+                              const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row,
+                              const float *position_rows, int64_t n_position_rows, const int64_t *segment_id,
+                              const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
+                              int64_t n_prefix, void *out, int64_t out_stride, int bf16, int *status, void *stream);
+int medtok_embed_sequence_rows_f32(const float *rows, const uint8_t *pad, int64_t batch, int64_t len, int width,
+                                   const float *position_rows, int64_t n_position_rows, const int64_t *segment_id,
+                                   const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
+                                   int64_t n_prefix, float *out, int *status, void *stream);
+int medtok_embed_sequence_rows_f16(const float *rows, const uint8_t *pad, int64_t batch, int64_t len, int width,
+                                   const float *position_rows, int64_t n_position_rows, const int64_t *segment_id,
+                                   const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
+                                   int64_t n_prefix, void *out, int bf16, int *status, void *stream);
+/* The gradients of the additive rows from the upstream gradient g fp32 [batch, n_prefix + len, width] (row stride = width), in fixed
+ * orders and without float atomics: two runs give the same bits.
+ * medtok_embed_sequence_segment_grad_f32: g_segment[b, v, :] = the sum of g[b, n_prefix + p, :] over the unpadded p with segment_id[b, p]
+ * == v (both segment terms receive this tensor): per MEDTOK_EMBED_SEQ_GRAD_CHUNK consecutive positions of a batch row in ascending
+ * position order, then the chunk sums in chunk order.  Ids outside [0, n_segments) and padded positions contribute nothing.  ws from the
+ * workspace query (host arithmetic: the chunk sums [batch, chunks, n_segments, width]; where it returns 0 -- no batch row, or len == 0 --
+ * ws may be NULL).  n_segments > MEDTOK_EMBED_SEQ_MAX_SEGMENTS is an error named as such, reported before any pointer is looked at (the
+ * query returns 0 for it).
+ * medtok_embed_sequence_position_grad_f32: g_position[p, :] = the sum over b ascending of g[b, n_prefix + p, :] at the unpadded (b, p),
+ * p < len; the rows len <= p < n_position_rows are zeros. */
+#define MEDTOK_EMBED_SEQ_GRAD_CHUNK 256
+size_t medtok_embed_sequence_grad_workspace_bytes(int64_t batch, int64_t len, int64_t n_segments, int width);
+int medtok_embed_sequence_segment_grad_f32(const float *g, const uint8_t *pad, const int64_t *segment_id, int64_t batch, int64_t len,
+                                           int64_t n_prefix, int64_t n_segments, int width, float *g_segment, void *ws, size_t ws_bytes,
+                                           void *stream);
+int medtok_embed_sequence_position_grad_f32(const float *g, const uint8_t *pad, int64_t batch, int64_t len, int64_t n_prefix, int width,
+                                            int64_t n_position_rows, float *g_position, void *stream);
 
 /* ---- fp32-accurate dense products on the fp16 matrix pipe (the projections around the cross-attention core:
  * nn.MultiheadAttention's in_proj / out_proj and the folded W_k / W_v products, vector_quantization_soft_one_new.py:17-51).

@@ -83,6 +83,15 @@ SIGNATURES = {
     "medtok_embed_pool_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "medtok_embed_pool_f32": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _int, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "medtok_embed_pool_miss_grad_f32": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
+    "medtok_embed_sequence_f32": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                         _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "medtok_embed_sequence_f16": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                         _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "medtok_embed_sequence_rows_f32": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "medtok_embed_sequence_rows_f16": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _int, _vp, _vp]),
+    "medtok_embed_sequence_grad_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
+    "medtok_embed_sequence_segment_grad_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
+    "medtok_embed_sequence_position_grad_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp]),
     "medtok_soft_vq_backward_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     "medtok_normalize_backward_f32": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp]),
     "medtok_normalize_backward_sparse_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _vp, _vp]),

@@ -674,32 +674,111 @@ class _EmbedProjectFunction(torch.autograd.Function):
     def backward(ctx, g):
         w, miss, index, pad_mask, tokens, weights, what = ctx.saved_tensors
         regions, e, has_bias = ctx.cfg
-        h, s, d = w.shape[0], len(regions), what.shape[1]
-        n = index.numel()
-        g = g.reshape(n, -1)[:, :h].float().contiguous()
-        index = index.reshape(-1)
-        pad_mask = None if pad_mask is None else pad_mask.reshape(-1)
-        wf = w.detach().float().contiguous()
-        dw = db = dmiss = None
-        if ctx.needs_input_grad[0]:
-            miss_d = None
-            if miss is not None:
-                miss_d = miss.detach().reshape(s, e)
-                miss_d = (torch.nn.functional.pad(miss_d, (0, d - e)) if d != e else miss_d).reshape(-1).contiguous()
-            dw = torch.zeros_like(wf)
-            for r0 in range(0, n, EMBED_PROJECT_GRAD_CHUNK):
-                r1 = min(n, r0 + EMBED_PROJECT_GRAD_CHUNK)
-                emb = ops.embed_codes(index[r0:r1], tokens, weights, what, regions, miss=miss_d,
-                                      pad_mask=None if pad_mask is None else pad_mask[r0:r1])
-                if d != e:
-                    emb = emb.view(r1 - r0, s, d)[:, :, :e].reshape(r1 - r0, s * e)
-                dw.add_(ops.small_gemm(g[r0:r1], emb, trans_a=True))
-        if has_bias and ctx.needs_input_grad[1]:
-            db = g.sum(0)
-        if miss is not None and ctx.needs_input_grad[2]:
-            g_rows = ops.embed_codes_miss_grad(g, index, tokens.shape[0], pad_mask) if n else g.new_zeros(h)
-            dmiss = ops.small_gemm(g_rows.view(1, h), wf).reshape(miss.shape)
-        return (dw, db, dmiss) + (None,) * 10
+        return _embed_project_grads(g, w, miss, index, pad_mask, tokens, weights, what, regions, e, has_bias, ctx.needs_input_grad[:3]) + (None,) * 10
+
+
+def _embed_project_grads(g, w, miss, index, pad_mask, tokens, weights, what, regions, e, has_bias, needs):
+    """(dW, db, d miss) of the folded lookup from the upstream gradient g [n, >= H] of its rows: the arithmetic _EmbedProjectFunction
+    documents, shared with _EmbedSequenceFunction (which feeds it g[:, P:])"""
+    h, s, d = w.shape[0], len(regions), what.shape[1]
+    n = index.numel()
+    g = g.reshape(n, g.shape[-1])[:, :h].float().contiguous()          # (not -1: n may be 0)
+    index = index.reshape(-1)
+    pad_mask = None if pad_mask is None else pad_mask.reshape(-1)
+    wf = w.detach().float().contiguous()
+    dw = db = dmiss = None
+    if needs[0]:
+        miss_d = None
+        if miss is not None:
+            miss_d = miss.detach().reshape(s, e)
+            miss_d = (torch.nn.functional.pad(miss_d, (0, d - e)) if d != e else miss_d).reshape(-1).contiguous()
+        dw = torch.zeros_like(wf)
+        for r0 in range(0, n, EMBED_PROJECT_GRAD_CHUNK):
+            r1 = min(n, r0 + EMBED_PROJECT_GRAD_CHUNK)
+            emb = ops.embed_codes(index[r0:r1], tokens, weights, what, regions, miss=miss_d,
+                                  pad_mask=None if pad_mask is None else pad_mask[r0:r1])
+            if d != e:
+                emb = emb.view(r1 - r0, s, d)[:, :, :e].reshape(r1 - r0, s * e)
+            dw.add_(ops.small_gemm(g[r0:r1], emb, trans_a=True))
+    if has_bias and needs[1]:
+        db = g.sum(0)
+    if miss is not None and needs[2]:
+        g_rows = ops.embed_codes_miss_grad(g, index, tokens.shape[0], pad_mask) if n else g.new_zeros(h)
+        dmiss = ops.small_gemm(g_rows.view(1, h), wf).reshape(miss.shape)
+    return dw, db, dmiss
+
+
+def _sequence_part_grads(g, needs, n_rows, segment_id, n_segments, pad_mask, n_prefix):
+    """(d position_rows, d segment_rows[0], d segment_rows[1], d prefix) from g fp32 [B, P + L, W]; needs: which of the four are wanted"""
+    dpos = dseg = dprefix = None
+    if needs[0]:
+        dpos = ops.embed_sequence_position_grad(g, n_rows, pad_mask, n_prefix)
+    if needs[1] or needs[2]:
+        dseg = ops.embed_sequence_segment_grad(g, segment_id, n_segments, pad_mask, n_prefix)
+    if needs[3]:
+        dprefix = g[:, :n_prefix].contiguous()
+    return dpos, dseg if needs[1] else None, dseg if needs[2] else None, dprefix
+
+
+class _EmbedSequenceFunction(torch.autograd.Function):
+    """MedTokEmbedding.sequence over the folded tables under autograd: one launch forward (ops.embed_sequence).  Backward from g
+    [B, P + L, Hp] (a 16-bit g is converted to fp32 first, which is exact; the padding columns are dropped), deterministic and without
+    float atomics:
+      d prefix                g[:, :P]
+      d position_rows         ops.embed_sequence_position_grad (b ascending)
+      d segment_rows[0], [1]  ops.embed_sequence_segment_grad, the same tensor for both terms (chunks of 256 positions, then chunk order)
+      dW, db, d miss          _EmbedProjectFunction's arithmetic on a contiguous copy of g[:, P:] (padded positions are the bias row: they
+                              count in db, as there)."""
+
+    @staticmethod
+    def forward(ctx, w, b, miss, position_rows, seg0, seg1, prefix, index, pad_mask, segment_id, tokens, weights, what, regions, e_dim, folded,
+                out_dtype, status):
+        table, row_regions, bias, miss_row = folded
+        terms = tuple(t for t in (seg0, seg1) if t is not None)
+        out = ops.embed_sequence(index, tokens, weights, table, row_regions, bias, miss_row=miss_row, pad_mask=pad_mask,
+                                 position_rows=position_rows, segment_id=segment_id, segment_rows=terms or None, prefix=prefix, width=w.shape[0],
+                                 out_dtype=out_dtype, status=status)
+        ctx.save_for_backward(w, miss, index, pad_mask, segment_id, tokens, weights, what)
+        ctx.cfg = (tuple(regions), int(e_dim), b is not None, None if position_rows is None else position_rows.shape[0],
+                   0 if seg0 is None else seg0.shape[1], 0 if prefix is None else prefix.shape[1])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        w, miss, index, pad_mask, segment_id, tokens, weights, what = ctx.saved_tensors
+        regions, e, has_bias, n_rows, n_segments, n_prefix = ctx.cfg
+        g = g[:, :, :w.shape[0]].float().contiguous()
+        needs = ctx.needs_input_grad
+        grads = (None, None, None)
+        if any(needs[:3]):
+            grads = _embed_project_grads(g[:, n_prefix:].contiguous(), w, miss, index, pad_mask, tokens, weights, what, regions, e, has_bias,
+                                         needs[:3])
+        return grads + _sequence_part_grads(g, needs[3:7], n_rows, segment_id, n_segments, pad_mask, n_prefix) + (None,) * 11
+
+
+class _EmbedSequenceRowsFunction(torch.autograd.Function):
+    """MedTokEmbedding.sequence over dense rows under autograd (ops.embed_sequence_rows): the lookup's fp32 rows [B, L, W] are an input,
+    so d rows = g[:, P:] flows on into the nodes that made them (the codebook's and the miss row's gradients, the unfolded projector's).
+    The additive parts' gradients are _EmbedSequenceFunction's."""
+
+    @staticmethod
+    def forward(ctx, rows, position_rows, seg0, seg1, prefix, pad_mask, segment_id, out_dtype, status):
+        terms = tuple(t for t in (seg0, seg1) if t is not None)
+        out = ops.embed_sequence_rows(rows, pad_mask=pad_mask, position_rows=position_rows, segment_id=segment_id, segment_rows=terms or None,
+                                      prefix=prefix, out_dtype=out_dtype, status=status)
+        ctx.save_for_backward(pad_mask, segment_id)
+        ctx.cfg = (None if position_rows is None else position_rows.shape[0], 0 if seg0 is None else seg0.shape[1],
+                   0 if prefix is None else prefix.shape[1])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pad_mask, segment_id = ctx.saved_tensors
+        n_rows, n_segments, n_prefix = ctx.cfg
+        g = g.float().contiguous()
+        needs = ctx.needs_input_grad
+        drows = g[:, n_prefix:].contiguous() if needs[0] else None
+        return (drows,) + _sequence_part_grads(g, needs[1:5], n_rows, segment_id, n_segments, pad_mask, n_prefix) + (None,) * 4
 
 
 def _lib_multi_max():

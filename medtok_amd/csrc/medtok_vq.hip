@@ -10,6 +10,7 @@
 //   assign_kernels.h      soft assignment, fixed-order fp64 sum
 //   decode_kernels.h      (token ids, weights) -> embedding, and its backward
 //   embed_kernels.h       code indices -> stored tokens -> embedding
+//   embed_sequence_kernels.h  the lookup's rows + position rows + segment rows behind prefix rows, and the additive rows' gradients
 //   embed_grad_kernels.h  the codebook's gradient through the lookup: sort keys, chunked per-row sums
 //   train_kernels.h       sparse backward, normalize backward, InfoNCE
 //   loss_kernels.h        alignment / orthogonality losses
@@ -1271,6 +1272,215 @@ extern "C" int medtok_embed_pool_miss_grad_f32(const float *g_out, int64_t g_str
                            (long)bags, width, (float *)ws);
     hipLaunchKernelGGL(embed_miss_grad_sum_kernel, dim3(col_blocks), dim3(256), 0, s, (const float *)ws, chunks, width, g_acc);
     return check_launch("embed_pool_miss_grad");
+}
+
+// ---- the consumer's input sequence behind the lookup: position rows, segment rows and prefix rows in the lookup's launch
+#include "embed_sequence_kernels.h"
+
+// a launch holds at most 2^32 threads along x: 2^24 - 1 blocks of 256
+static const int64_t kSeqMaxBlocks = 0xffffffffll / 256;
+
+// the checks every medtok_embed_sequence_* entry shares: shapes and which parts are present, before any pointer of a tensor is looked at
+static int sequence_parts(const char *fn, int64_t batch, int64_t len, int width, const float *position_rows, int64_t n_position_rows,
+                          const int64_t *segment_id, const float *segment_rows0, const float *segment_rows1, int64_t n_segments,
+                          const float *prefix, int64_t n_prefix, EmbedSeqParts &parts)
+{
+    if (batch < 0 || len < 0 || n_prefix < 0 || width < 1)
+        return fail("%s: bad shape batch=%ld len=%ld n_prefix=%ld width=%d", fn, (long)batch, (long)len, (long)n_prefix, width);
+    if (batch >= (1ll << 31) || len >= (1ll << 31) || n_prefix >= (1ll << 31) || batch * (n_prefix + len) >= (1ll << 31))
+        return fail("%s: batch * (n_prefix + len) = %ld x (%ld + %ld) rows reach 2^31", fn, (long)batch, (long)n_prefix, (long)len);
+    if (segment_rows1 && !segment_rows0) return fail("%s: segment_rows1 without segment_rows0", fn);
+    if ((segment_id != nullptr) != (segment_rows0 != nullptr)) return fail("%s: segment_id and segment_rows0 come together", fn);
+    if (segment_id && (n_segments < 1 || n_segments > MEDTOK_EMBED_SEQ_MAX_SEGMENTS))
+        return fail("%s: n_segments=%ld unsupported (1 .. %d)", fn, (long)n_segments, MEDTOK_EMBED_SEQ_MAX_SEGMENTS);
+    if (position_rows && n_position_rows < len)
+        return fail("%s: position_rows holds %ld rows, fewer than len=%ld", fn, (long)n_position_rows, (long)len);
+    if (batch > 0 && n_prefix > 0 && !prefix) return fail("%s: prefix is required for n_prefix=%ld", fn, (long)n_prefix);
+    parts.position_rows = position_rows;
+    parts.segment_id = segment_id;
+    parts.segment_rows0 = segment_rows0;
+    parts.segment_rows1 = segment_rows1;
+    parts.prefix = n_prefix > 0 ? prefix : nullptr;
+    parts.n_segments = segment_id ? (long)n_segments : 1;
+    parts.n_prefix = (long)n_prefix;
+    return 0;
+}
+
+// both output widths of medtok_embed_sequence_*: embed_project's checks, the parts, then one launch
+template <typename OUT>
+static int embed_sequence_launch(const char *fn, const int64_t *index, const uint8_t *pad, int64_t batch, int64_t len, const int64_t *tokens,
+                                 const float *weights, int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp,
+                                 const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row,
+                                 const float *position_rows, int64_t n_position_rows, const int64_t *segment_id, const float *segment_rows0,
+                                 const float *segment_rows1, int64_t n_segments, const float *prefix, int64_t n_prefix, OUT *out,
+                                 int64_t out_stride, int *status, void *stream)
+{
+    DecodeRegions reg;
+    EmbedSeqParts parts;
+    if (int rc = sequence_parts(fn, batch, len, hp, position_rows, n_position_rows, segment_id, segment_rows0, segment_rows1, n_segments, prefix,
+                                n_prefix, parts))
+        return rc;
+    if (int rc = decode_args(fn, batch * len, slots, topk, n_rows, hp, row_lo, row_size, reg)) return rc;
+    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
+    if (slots * topk > 64) return fail("%s: slots * topk = %d entries per code exceed one wavefront", fn, slots * topk);
+    if (out_stride == 0) out_stride = hp;
+    if (out_stride < hp || (out_stride & 3)) return fail("%s: out_stride must be >= hp and a multiple of 4", fn);
+    const int64_t items = batch * (n_prefix + len);
+    if (items == 0) return 0;
+    if (!tokens || !weights || !table || !bias || !out || (len > 0 && !index))
+        return fail("%s: index, tokens, weights, table, bias and out are required", fn);
+    hipStream_t s = (hipStream_t)stream;
+    // the smallest group that holds the code's slots * topk entries and, up to a wavefront, covers the row in one float4 pass
+    int lanes = 16;
+    while (lanes < 64 && (lanes < slots * topk || lanes * 4 < hp)) lanes *= 2;
+    const int64_t blocks = (items + 256 / lanes - 1) / (256 / lanes);
+    if (blocks > kSeqMaxBlocks) return fail("%s: %ld rows exceed one launch (%ld blocks of 256 threads)", fn, (long)items, (long)kSeqMaxBlocks);
+#define MEDTOK_SEQUENCE_LAUNCH(LANES, MAXK)                                                                                              \
+    hipLaunchKernelGGL((embed_sequence_kernel<LANES, MAXK, OUT>), dim3((unsigned)blocks), dim3(256), 0, s, index, pad, (long)items, (long)len, \
+                       tokens, weights, (long)num_codes, slots, topk, table, hp, reg, bias, miss_row, parts, out, (long)out_stride, status)
+#define MEDTOK_SEQUENCE_LANES(LANES) do { if (topk <= 8) MEDTOK_SEQUENCE_LAUNCH(LANES, 8); else MEDTOK_SEQUENCE_LAUNCH(LANES, MEDTOK_MAX_TOPK); } while (0)
+    if (lanes == 16) MEDTOK_SEQUENCE_LANES(16); else if (lanes == 32) MEDTOK_SEQUENCE_LANES(32); else MEDTOK_SEQUENCE_LANES(64);
+#undef MEDTOK_SEQUENCE_LANES
+#undef MEDTOK_SEQUENCE_LAUNCH
+    return check_launch(fn);
+}
+
+extern "C" int medtok_embed_sequence_f32(const int64_t *index, const uint8_t *pad, int64_t batch, int64_t len, const int64_t *tokens,
+                                         const float *weights, int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows,
+                                         int hp, const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row,
+                                         const float *position_rows, int64_t n_position_rows, const int64_t *segment_id,
+                                         const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
+                                         int64_t n_prefix, float *out, int64_t out_stride, int *status, void *stream)
+{
+    return embed_sequence_launch<float>("embed_sequence", index, pad, batch, len, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo,
+                                        row_size, bias, miss_row, position_rows, n_position_rows, segment_id, segment_rows0, segment_rows1,
+                                        n_segments, prefix, n_prefix, out, out_stride, status, stream);
+}
+
+extern "C" int medtok_embed_sequence_f16(const int64_t *index, const uint8_t *pad, int64_t batch, int64_t len, const int64_t *tokens,
+                                         const float *weights, int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows,
+                                         int hp, const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row,
+                                         const float *position_rows, int64_t n_position_rows, const int64_t *segment_id,
+                                         const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
+                                         int64_t n_prefix, void *out, int64_t out_stride, int bf16, int *status, void *stream)
+{
+    if (bf16)
+        return embed_sequence_launch<__bf16>("embed_sequence_f16(bf16)", index, pad, batch, len, tokens, weights, num_codes, slots, topk, table,
+                                             n_rows, hp, row_lo, row_size, bias, miss_row, position_rows, n_position_rows, segment_id,
+                                             segment_rows0, segment_rows1, n_segments, prefix, n_prefix, (__bf16 *)out, out_stride, status, stream);
+    return embed_sequence_launch<_Float16>("embed_sequence_f16", index, pad, batch, len, tokens, weights, num_codes, slots, topk, table, n_rows, hp,
+                                           row_lo, row_size, bias, miss_row, position_rows, n_position_rows, segment_id, segment_rows0,
+                                           segment_rows1, n_segments, prefix, n_prefix, (_Float16 *)out, out_stride, status, stream);
+}
+
+// both output widths of medtok_embed_sequence_rows_*: the epilogue over dense fp32 rows
+template <typename OUT>
+static int embed_sequence_rows_launch(const char *fn, const float *rows, const uint8_t *pad, int64_t batch, int64_t len, int width,
+                                      const float *position_rows, int64_t n_position_rows, const int64_t *segment_id, const float *segment_rows0,
+                                      const float *segment_rows1, int64_t n_segments, const float *prefix, int64_t n_prefix, OUT *out, int *status,
+                                      void *stream)
+{
+    EmbedSeqParts parts;
+    if (int rc = sequence_parts(fn, batch, len, width, position_rows, n_position_rows, segment_id, segment_rows0, segment_rows1, n_segments, prefix,
+                                n_prefix, parts))
+        return rc;
+    const int64_t items = batch * (n_prefix + len);
+    if (items == 0) return 0;
+    if (!out || (len > 0 && !rows)) return fail("%s: rows and out are required", fn);
+    const int vec = (width & 3) ? 1 : 4;
+    const int64_t blocks = (items * (width / vec) + 255) / 256;   // items < 2^31, width < 2^31: no overflow
+    if (blocks > kSeqMaxBlocks) return fail("%s: %ld rows of %d exceed one launch (%ld blocks of 256 threads)", fn, (long)items, width, (long)kSeqMaxBlocks);
+    hipStream_t s = (hipStream_t)stream;
+    if (vec == 4)
+        hipLaunchKernelGGL((embed_sequence_rows_kernel<4, OUT>), dim3((unsigned)blocks), dim3(256), 0, s, rows, pad, (long)items, (long)len, width, parts,
+                           out, status);
+    else
+        hipLaunchKernelGGL((embed_sequence_rows_kernel<1, OUT>), dim3((unsigned)blocks), dim3(256), 0, s, rows, pad, (long)items, (long)len, width, parts,
+                           out, status);
+    return check_launch(fn);
+}
+
+extern "C" int medtok_embed_sequence_rows_f32(const float *rows, const uint8_t *pad, int64_t batch, int64_t len, int width,
+                                              const float *position_rows, int64_t n_position_rows, const int64_t *segment_id,
+                                              const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
+                                              int64_t n_prefix, float *out, int *status, void *stream)
+{
+    return embed_sequence_rows_launch<float>("embed_sequence_rows", rows, pad, batch, len, width, position_rows, n_position_rows, segment_id,
+                                             segment_rows0, segment_rows1, n_segments, prefix, n_prefix, out, status, stream);
+}
+
+extern "C" int medtok_embed_sequence_rows_f16(const float *rows, const uint8_t *pad, int64_t batch, int64_t len, int width,
+                                              const float *position_rows, int64_t n_position_rows, const int64_t *segment_id,
+                                              const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
+                                              int64_t n_prefix, void *out, int bf16, int *status, void *stream)
+{
+    if (bf16)
+        return embed_sequence_rows_launch<__bf16>("embed_sequence_rows_f16(bf16)", rows, pad, batch, len, width, position_rows, n_position_rows,
+                                                  segment_id, segment_rows0, segment_rows1, n_segments, prefix, n_prefix, (__bf16 *)out, status, stream);
+    return embed_sequence_rows_launch<_Float16>("embed_sequence_rows_f16", rows, pad, batch, len, width, position_rows, n_position_rows, segment_id,
+                                                segment_rows0, segment_rows1, n_segments, prefix, n_prefix, (_Float16 *)out, status, stream);
+}
+
+// the partial sums [batch, chunks, n_segments, width] fp32 of medtok_embed_sequence_segment_grad_f32; 0 for a shape the entry refuses
+extern "C" size_t medtok_embed_sequence_grad_workspace_bytes(int64_t batch, int64_t len, int64_t n_segments, int width)
+{
+    if (batch < 0 || len < 0 || width < 1 || n_segments < 1 || n_segments > MEDTOK_EMBED_SEQ_MAX_SEGMENTS) return 0;
+    if (batch >= (1ll << 31) || len >= (1ll << 31)) return 0;
+    const size_t chunks = (size_t)((len + MEDTOK_EMBED_SEQ_GRAD_CHUNK - 1) / MEDTOK_EMBED_SEQ_GRAD_CHUNK);
+    return ((size_t)batch * chunks * (size_t)n_segments * (size_t)width * sizeof(float) + 255) & ~(size_t)255;
+}
+
+extern "C" int medtok_embed_sequence_segment_grad_f32(const float *g, const uint8_t *pad, const int64_t *segment_id, int64_t batch, int64_t len,
+                                                      int64_t n_prefix, int64_t n_segments, int width, float *g_segment, void *ws, size_t ws_bytes,
+                                                      void *stream)
+{
+    const char *fn = "embed_sequence_segment_grad";
+    if (n_segments < 1 || n_segments > MEDTOK_EMBED_SEQ_MAX_SEGMENTS)
+        return fail("%s: n_segments=%ld unsupported (1 .. %d)", fn, (long)n_segments, MEDTOK_EMBED_SEQ_MAX_SEGMENTS);
+    if (batch < 0 || len < 0 || n_prefix < 0 || width < 1)
+        return fail("%s: bad shape batch=%ld len=%ld n_prefix=%ld width=%d", fn, (long)batch, (long)len, (long)n_prefix, width);
+    if (batch >= (1ll << 31) || len >= (1ll << 31) || n_prefix >= (1ll << 31) || batch * (n_prefix + len) >= (1ll << 31))
+        return fail("%s: batch * (n_prefix + len) = %ld x (%ld + %ld) rows reach 2^31", fn, (long)batch, (long)n_prefix, (long)len);
+    if (batch == 0) return 0;
+    if (!g_segment) return fail("%s: g_segment is required", fn);
+    const int64_t chunks = (len + MEDTOK_EMBED_SEQ_GRAD_CHUNK - 1) / MEDTOK_EMBED_SEQ_GRAD_CHUNK;
+    if (chunks && (!g || !segment_id)) return fail("%s: g and segment_id are required", fn);
+    // the widest power-of-two column tile (4 .. 256) whose [n_segments][tile] accumulators fit 64 KiB of LDS, no wider than the rows need
+    int tile = 256;
+    while (tile > 4 && ((int64_t)n_segments * tile * 4 > 65536 || tile / 2 >= width)) tile /= 2;
+    const int64_t col_blocks = (width + tile - 1) / tile;
+    const int64_t total = batch * n_segments * (int64_t)width;
+    if (batch * chunks > kSeqMaxBlocks || col_blocks > 65535 || (total + 255) / 256 > kSeqMaxBlocks)
+        return fail("%s: batch=%ld x len=%ld x n_segments=%ld x width=%d exceed one launch", fn, (long)batch, (long)len, (long)n_segments, width);
+    if (chunks && (!ws || ws_bytes < medtok_embed_sequence_grad_workspace_bytes(batch, len, n_segments, width)))
+        return fail("%s: workspace too small (%zu bytes given)", fn, ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    if (chunks)
+        hipLaunchKernelGGL(embed_sequence_segment_grad_partial_kernel, dim3((unsigned)(batch * chunks), (unsigned)col_blocks),
+                           dim3(tile < 64 ? 64 : tile), (size_t)n_segments * tile * sizeof(float), s, g, pad, segment_id, (long)len, (int)chunks,
+                           (long)n_prefix, (int)n_segments, width, tile, (float *)ws);
+    hipLaunchKernelGGL(embed_sequence_segment_grad_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float *)ws, (long)total,
+                       (int)chunks, (int)n_segments, width, g_segment);
+    return check_launch(fn);
+}
+
+extern "C" int medtok_embed_sequence_position_grad_f32(const float *g, const uint8_t *pad, int64_t batch, int64_t len, int64_t n_prefix, int width,
+                                                       int64_t n_position_rows, float *g_position, void *stream)
+{
+    const char *fn = "embed_sequence_position_grad";
+    if (batch < 0 || len < 0 || n_prefix < 0 || width < 1 || n_position_rows < len)
+        return fail("%s: bad shape batch=%ld len=%ld n_prefix=%ld width=%d n_position_rows=%ld", fn, (long)batch, (long)len, (long)n_prefix, width,
+                    (long)n_position_rows);
+    if (batch >= (1ll << 31) || len >= (1ll << 31) || n_prefix >= (1ll << 31) || batch * (n_prefix + len) >= (1ll << 31))
+        return fail("%s: batch * (n_prefix + len) = %ld x (%ld + %ld) rows reach 2^31", fn, (long)batch, (long)n_prefix, (long)len);
+    if (n_position_rows == 0) return 0;
+    if (n_position_rows >= (1ll << 31)) return fail("%s: n_position_rows=%ld unsupported", fn, (long)n_position_rows);
+    const int64_t total = n_position_rows * (int64_t)width;
+    if ((total + 255) / 256 > kSeqMaxBlocks) return fail("%s: %ld rows of %d exceed one launch", fn, (long)n_position_rows, width);
+    if (!g_position || (batch > 0 && len > 0 && !g)) return fail("%s: g and g_position are required", fn);
+    hipLaunchKernelGGL(embed_sequence_position_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, pad,
+                       (long)batch, (long)len, (long)n_prefix, width, (long)total, g_position);
+    return check_launch(fn);
 }
 
 // ================================================================= training half: sparse backward, normalize backward, InfoNCE

@@ -23,7 +23,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import _EmbedCodesFunction, _EmbedCodesTrainFunction, _EmbedPoolFunction, _EmbedProjectFunction, small_linear
+from .autograd import (_EmbedCodesFunction, _EmbedCodesTrainFunction, _EmbedPoolFunction, _EmbedProjectFunction, _EmbedSequenceFunction,
+                       _EmbedSequenceRowsFunction, small_linear)
 
 DEFAULT_TYPES = ("text", "graph", "shared", "shared")
 
@@ -205,6 +206,95 @@ class MedTokEmbedding(nn.Module):
         bad = (word & -word).bit_length() - 1
         raise ValueError(f"MedTokEmbedding: slot {bad} ({self.types[bad]!r}) of the token table holds an id outside [0, {regions[bad][1]}); "
                          f"slots with bad ids: {[i for i in range(len(regions)) if word >> i & 1]}")
+
+    # ------------------------------------------------------------------ the consumer's input sequence
+    def sequence(self, index, padding_mask=None, *, position_rows=None, segment_id=None, segment_rows=None, prefix=None, validate: bool = True,
+                 out_dtype=None):
+        """index int64 [B, L] -> (seq [B, P + L, W], key_padding_mask bool [B, P + L]): the input sequence the reference's EHR model
+        assembles from `forward`'s rows before its first transformer layer (EHRModel_token.py:220-232, PositionalEncoding.forward
+        :65-78), in the lookup's launch.  W is what `forward` returns per position (H with a projector, S * e_dim without).
+
+        position_rows fp32 [>= L, W]: the consumer's pe[:L], or a learned table.  segment_id int64 [B, L] (the consumer's
+        visit_id[:, :, 0]) with segment_rows, one fp32 [B, V, W] tensor or a sequence of at most ops.EMBED_SEQ_MAX_TERMS of them: the time
+        embeddings computed per VISIT (embedding the gathered timestamps equals gathering the embedded timestamps, value for value, and
+        [B, V, W] is L / V times smaller than what the reference gathers); V <= ops.EMBED_SEQ_MAX_SEGMENTS.  prefix fp32 [B, P, W]: the
+        rows the consumer puts in front (cls, gender, ethnicity), copied into seq[:, :P].  Every part may be absent; with none of them seq
+        is forward(index, padding_mask).  With r = forward(index, padding_mask, out_dtype=torch.float32)[b, p]:
+
+            padded position      seq[b, P + p] = r (the bias row, or zeros without a projector); nothing is added, and neither
+                                 index[b, p] nor segment_id[b, p] is read
+            unpadded position    seq[b, P + p] = ((r + position_rows[p]) + segment_rows[0][b, g]) + segment_rows[1][b, g],  g = segment_id[b, p]
+
+        plain fp32 additions in that order (the reference's ((x + pe) + t_within) + t_between), continuing from the fp32 value of the
+        lookup: in fp32 seq[:, P:] is bit for bit torch.where(mask, r, ((r + pe) + R0[b, g]) + R1[b, g]).  A miss position and, with
+        validate=False, a bad code index take the adds like any unpadded position.  A 16-bit output rounds the finished fp32 value once.
+        key_padding_mask is padding_mask with P False columns in front (all False without a mask).  Deviation from the reference: it
+        adds the terms at padded positions too; those positions are masked as keys and only the CLS row is read, so nothing downstream
+        sees the difference.  Dropout stays outside: PositionalEncoding's dropout(0.2) is torch's, applied by the caller to seq[:, P:].
+
+        validate=True reads the status back and raises the ValueErrors of `forward` first ("code index", then the first slot with a bad
+        id), then one naming the "segment id" for an unpadded g outside [0, V); validate=False reads nothing (such a position gets no
+        segment term), so a step -- forward and backward -- can be captured in a HIP graph.  Gradients: prefix, position_rows and
+        segment_rows get theirs from fixed-order sums without float atomics (ops.embed_sequence_position_grad / _segment_grad: two
+        backward runs give the same bits); the projector, miss_emb and a training codebook get what `forward` gives them from
+        g[:, P:].  Over folded tables (the rule of `forward`) the whole row is made in one launch (ops.embed_sequence); otherwise the
+        lookup's fp32 rows go through one elementwise launch (ops.embed_sequence_rows)."""
+        name = "MedTokEmbedding.sequence"
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+            raise ValueError(f"MedTokEmbedding: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+        if index.dim() != 2:
+            raise ValueError(f"{name} takes index [B, L], got {tuple(index.shape)}")
+        p, q = getattr(self, "projector", None), self.quantizer
+        width = self.embedding_dim if p is None else p.out_features
+        padding_mask, out_dtype = self._checked(index, padding_mask, out_dtype, None, width)
+        batch, length = index.shape
+        position_rows, segment_id, terms, prefix, n_segments, n_prefix = ops._sequence_parts(name, batch, length, width, position_rows, segment_id,
+                                                                                             segment_rows, prefix)
+        seg0, seg1 = (terms + (None, None))[:2]
+        parts = (position_rows, seg0, seg1, prefix)
+        grad_on = torch.is_grad_enabled()
+        parts_grad = grad_on and any(t is not None and t.requires_grad for t in parts)
+        dev = self.tokens.device
+        regions = self._regions()
+        fold = False
+        if p is not None:
+            if p.weight.dtype != torch.float32:
+                raise ValueError(f"MedTokEmbedding: the projector must be fp32 (every product behind the lookup is), got {p.weight.dtype}")
+            want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
+            norm = None if want_codebook else q._normalised_codebook()
+            fold = False if want_codebook else self.fold
+            if fold is None:
+                cache = self._fold_cache
+                fold = self.fold_rule(index.numel(), cache is not None and cache[0] == self._fold_key(norm))
+        status = torch.zeros(1, dtype=torch.int32, device=dev) if validate else None
+        if fold:
+            folded = self._folded(norm)
+            if parts_grad or (grad_on and any(t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb))):
+                seq = _EmbedSequenceFunction.apply(p.weight, p.bias, self.miss_emb, position_rows, seg0, seg1, prefix, index, padding_mask,
+                                                   segment_id, self.tokens, self.weights, norm[0], tuple(regions), int(q.e_dim), folded, out_dtype,
+                                                   status)
+            else:
+                seq = ops.embed_sequence(index, self.tokens, self.weights, *folded[:3], miss_row=folded[3], pad_mask=padding_mask,
+                                         position_rows=position_rows, segment_id=segment_id, segment_rows=terms or None, prefix=prefix,
+                                         width=width, out_dtype=out_dtype, status=status)
+            if seq.shape[2] != width:
+                seq = seq[:, :, :width].contiguous()
+        else:
+            rows = self.forward(index, padding_mask, validate=validate, out_dtype=torch.float32)     # (raises its own errors first)
+            if parts_grad or rows.requires_grad:
+                seq = _EmbedSequenceRowsFunction.apply(rows, position_rows, seg0, seg1, prefix, padding_mask, segment_id, out_dtype, status)
+            else:
+                seq = ops.embed_sequence_rows(rows, pad_mask=padding_mask, position_rows=position_rows, segment_id=segment_id,
+                                              segment_rows=terms or None, prefix=prefix, out_dtype=out_dtype, status=status)
+        if validate:
+            word = int(status.item())
+            self._raise_on(word & ~(1 << ops.EMBED_BAD_SEGMENT_BIT), regions)
+            if word >> ops.EMBED_BAD_SEGMENT_BIT & 1:
+                raise ValueError(f"MedTokEmbedding: a segment id outside [0, {n_segments}) at a position the padding mask does not cover")
+        keys = torch.zeros((batch, n_prefix + length), dtype=torch.bool, device=seq.device)
+        if padding_mask is not None:
+            keys[:, n_prefix:] = padding_mask.to(seq.device) != 0
+        return seq, keys
 
     # ------------------------------------------------------------------ bag pooling
     def pooled(self, index, padding_mask=None, normalize: bool = True, validate: bool = True):

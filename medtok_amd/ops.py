@@ -694,6 +694,229 @@ def embed_project(index, tokens, weights, table, row_regions, bias, miss_row=Non
     return res.view(*index.shape, hp) if out is None else out
 
 
+EMBED_BAD_SEGMENT_BIT = 5                   # MEDTOK_EMBED_BAD_SEGMENT_BIT: an unpadded position's segment id outside [0, V)
+EMBED_SEQ_MAX_TERMS = 2                     # MEDTOK_EMBED_SEQ_MAX_TERMS: segment terms per call
+EMBED_SEQ_MAX_SEGMENTS = 4096               # MEDTOK_EMBED_SEQ_MAX_SEGMENTS: V (the gradient keeps V x 4 columns of sums in 64 KiB of LDS)
+EMBED_SEQ_GRAD_CHUNK = 256                  # positions per partial sum of embed_sequence_segment_grad (MEDTOK_EMBED_SEQ_GRAD_CHUNK: part of the bits)
+
+
+def _sequence_parts(fn, batch, length, width, position_rows, segment_id, segment_rows, prefix):
+    """The shape and dtype checks of the parts embed_sequence / embed_sequence_rows add to the [batch, length, width] rows ->
+    (position_rows, segment_id, terms, prefix, n_segments, n_prefix); nothing here looks at a device."""
+    def fp32(t, name, dims):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != dims or t.shape[-1] != width:
+            raise ValueError(f"{fn}: {name} must be an fp32 {dims}-D tensor of width {width}, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    if position_rows is not None:
+        fp32(position_rows, "position_rows", 2)
+        if position_rows.shape[0] < length:
+            raise ValueError(f"{fn}: position_rows holds {position_rows.shape[0]} rows, fewer than the {length} positions")
+    terms = ()
+    if segment_rows is not None:
+        terms = (segment_rows,) if isinstance(segment_rows, torch.Tensor) else tuple(segment_rows)
+        if not 1 <= len(terms) <= EMBED_SEQ_MAX_TERMS:
+            raise ValueError(f"{fn}: segment_rows must be one tensor or a sequence of 1 .. {EMBED_SEQ_MAX_TERMS} tensors, got {len(terms)} terms")
+    if terms and segment_id is None:
+        raise ValueError(f"{fn}: segment_rows without segment_id")
+    if segment_id is not None and not terms:
+        raise ValueError(f"{fn}: segment_id without segment_rows")
+    n_segments = 0
+    if terms:
+        if not isinstance(segment_id, torch.Tensor) or segment_id.dtype != torch.int64 or tuple(segment_id.shape) != (batch, length):
+            raise ValueError(f"{fn}: segment_id must be an int64 [{batch}, {length}] tensor, got {getattr(segment_id, 'dtype', type(segment_id))} "
+                             f"{tuple(getattr(segment_id, 'shape', ()))}")
+        for i, t in enumerate(terms):
+            fp32(t, f"segment_rows[{i}]", 3)
+            if t.shape[0] != batch or t.shape[1] != terms[0].shape[1]:
+                raise ValueError(f"{fn}: segment_rows[{i}] must be [{batch}, V, {width}] with one V for all terms, got {tuple(t.shape)}")
+        n_segments = int(terms[0].shape[1])
+        if not 1 <= n_segments <= EMBED_SEQ_MAX_SEGMENTS:
+            raise ValueError(f"{fn}: V = {n_segments} segments unsupported (1 .. {EMBED_SEQ_MAX_SEGMENTS})")
+    n_prefix = 0
+    if prefix is not None:
+        fp32(prefix, "prefix", 3)
+        if prefix.shape[0] != batch:
+            raise ValueError(f"{fn}: prefix must be [{batch}, P, {width}], got {tuple(prefix.shape)}")
+        n_prefix = int(prefix.shape[1])
+    if batch * (n_prefix + length) >= 1 << 31:
+        raise ValueError(f"{fn}: {batch} x ({n_prefix} + {length}) rows reach 2^31: split the batch")
+    return position_rows, segment_id, terms, prefix, n_segments, n_prefix
+
+
+def _sequence_parts_on_device(position_rows, segment_id, terms, prefix, columns=0):
+    """the parts as contiguous device tensors; columns > 0: that many zero columns are appended (the folded tables' rows are hp wide)"""
+    def dev(t, name):
+        t = _dev(t.detach(), name)
+        return torch.nn.functional.pad(t, (0, columns)) if columns else t
+    position_rows = None if position_rows is None else dev(position_rows, "position_rows")
+    segment_id = None if segment_id is None else _dev(segment_id, "segment_id", torch.int64)
+    terms = tuple(dev(t, f"segment_rows[{i}]") for i, t in enumerate(terms))
+    prefix = None if prefix is None or prefix.shape[1] == 0 else dev(prefix, "prefix")
+    return position_rows, segment_id, terms, prefix
+
+
+def embed_sequence(index, tokens, weights, table, row_regions, bias, miss_row=None, pad_mask=None, position_rows=None, segment_id=None,
+                   segment_rows=None, prefix=None, width=None, out_dtype=torch.float32, status=None):
+    """embed_project's rows with the consumer's sequence assembly in the same launch -> (seq [B, P + L, Hp]).
+
+    index int64 [B, L]; tokens .. pad_mask, out_dtype: as embed_project.  With r0 the row embed_project gives for position (b, p):
+      padded position      seq[b, P + p] = r0 (the bias row); nothing is added; neither index[b, p] nor segment_id[b, p] is read
+      unpadded position    seq[b, P + p] = ((r0 + position_rows[p]) + segment_rows[0][b, g]) + segment_rows[1][b, g],  g = segment_id[b, p]
+      seq[b, :P]           prefix[b]
+    plain fp32 additions in that order on the fp32 value of the lookup's chain: in fp32 the bits of torch adding the tensors to
+    embed_project's result one after the other.  position_rows fp32 [>= L, width]; segment_id int64 [B, L]; segment_rows: one fp32
+    [B, V, width] tensor or a sequence of at most EMBED_SEQ_MAX_TERMS, V <= EMBED_SEQ_MAX_SEGMENTS; prefix fp32 [B, P, width]; each may be
+    None.  width (default Hp): the width of these tensors, Hp or the projector's H with pad_dim(H) == Hp (zero columns are appended
+    here).  A g outside [0, V) adds no segment term and sets bit EMBED_BAD_SEGMENT_BIT of `status`; a miss position and a bad code index
+    take the adds like any unpadded position.  Nothing is read back here."""
+    fn = "embed_sequence"
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+    if index.dim() != 2:
+        raise ValueError(f"{fn}: index must be [batch, length], got {tuple(index.shape)}")
+    if out_dtype not in EMBED_OUT_DTYPES:
+        raise ValueError(f"{fn}: out_dtype must be one of {EMBED_OUT_DTYPES}, got {out_dtype!r}")
+    pad_mask = _embed_mask(fn, pad_mask, index)
+    tokens, weights, row_regions = _decode_shapes(fn, tokens, weights, table, row_regions)
+    num_codes, s, k = tokens.shape
+    if num_codes < 1:
+        raise ValueError(f"{fn}: the token table is empty")
+    if s * k > 64:
+        raise ValueError(f"{fn}: {s} slots of {k} ids are more than the 64 entries per code the kernel takes")
+    hp = table.shape[1]
+    width = hp if width is None else int(width)
+    if pad_dim(width) != hp:
+        raise ValueError(f"{fn}: width = {width} does not pad to the tables' {hp} columns")
+    for name, t in (("bias", bias), ("miss_row", miss_row)):
+        if (t is not None or name == "bias") and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (hp,)):
+            raise ValueError(f"{fn}: {name} must be fp32 [{hp}], got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    batch, length = index.shape
+    parts = _sequence_parts(fn, batch, length, width, position_rows, segment_id, segment_rows, prefix)
+    n_segments, n_prefix = parts[4:]
+    index = _dev(index, "index", torch.int64)
+    tokens, weights, table, los, sizes = _decode_on_device(tokens, weights, table, row_regions)
+    bias = _dev(bias, "bias")
+    miss_row = None if miss_row is None else _dev(miss_row, "miss_row")
+    pad_mask = _embed_mask_on_device(pad_mask)
+    position_rows, segment_id, terms, prefix = _sequence_parts_on_device(*parts[:4], columns=hp - width)
+    if status is not None:
+        status = _dev(status, "status", torch.int32)
+    res = torch.empty((batch, n_prefix + length, hp), dtype=out_dtype, device=table.device)
+    lib = _lib.load()
+    with _on(table.device):
+        head = (index.data_ptr(), _ptr(pad_mask), batch, length, tokens.data_ptr(), weights.data_ptr(), num_codes, s, k, table.data_ptr(),
+                table.shape[0], hp, los, sizes, bias.data_ptr(), _ptr(miss_row), _ptr(position_rows),
+                0 if position_rows is None else position_rows.shape[0], _ptr(segment_id), _ptr(terms[0] if terms else None),
+                _ptr(terms[1] if len(terms) > 1 else None), n_segments, _ptr(prefix), n_prefix, res.data_ptr(), hp)
+        if out_dtype == torch.float32:
+            _lib.check(lib.medtok_embed_sequence_f32(*head, _ptr(status), _stream(table)), "medtok_embed_sequence_f32")
+        else:
+            _lib.check(lib.medtok_embed_sequence_f16(*head, int(out_dtype == torch.bfloat16), _ptr(status), _stream(table)), "medtok_embed_sequence_f16")
+    return res
+
+
+def embed_sequence_rows(rows, pad_mask=None, position_rows=None, segment_id=None, segment_rows=None, prefix=None, out_dtype=torch.float32,
+                        status=None):
+    """embed_sequence over dense rows: rows fp32 [B, L, W] (what a lookup that does not run over folded tables returned, any W >= 1) in
+    place of the tables -> seq [B, P + L, W] of out_dtype.  pad_mask bool / uint8 [B, L]; the parts, the order of the additions, the
+    padded positions (rows[b, p] as it stands), the status bit and the single rounding of a 16-bit output: as embed_sequence, every
+    tensor W wide.  Elementwise: place, add, cast."""
+    fn = "embed_sequence_rows"
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] < 1:
+        raise ValueError(f"{fn}: rows must be an fp32 [batch, length, width] tensor, got {getattr(rows, 'dtype', type(rows))} "
+                         f"{tuple(getattr(rows, 'shape', ()))}")
+    if out_dtype not in EMBED_OUT_DTYPES:
+        raise ValueError(f"{fn}: out_dtype must be one of {EMBED_OUT_DTYPES}, got {out_dtype!r}")
+    batch, length, width = rows.shape
+    pad_mask = _embed_mask(fn, pad_mask, rows[:, :, 0])
+    parts = _sequence_parts(fn, batch, length, width, position_rows, segment_id, segment_rows, prefix)
+    n_segments, n_prefix = parts[4:]
+    rows = _dev(rows.detach(), "rows")
+    pad_mask = _embed_mask_on_device(pad_mask)
+    position_rows, segment_id, terms, prefix = _sequence_parts_on_device(*parts[:4])
+    if status is not None:
+        status = _dev(status, "status", torch.int32)
+    res = torch.empty((batch, n_prefix + length, width), dtype=out_dtype, device=rows.device)
+    lib = _lib.load()
+    with _on(rows.device):
+        head = (rows.data_ptr(), _ptr(pad_mask), batch, length, width, _ptr(position_rows), 0 if position_rows is None else position_rows.shape[0],
+                _ptr(segment_id), _ptr(terms[0] if terms else None), _ptr(terms[1] if len(terms) > 1 else None), n_segments, _ptr(prefix), n_prefix,
+                res.data_ptr())
+        if out_dtype == torch.float32:
+            _lib.check(lib.medtok_embed_sequence_rows_f32(*head, _ptr(status), _stream(rows)), "medtok_embed_sequence_rows_f32")
+        else:
+            _lib.check(lib.medtok_embed_sequence_rows_f16(*head, int(out_dtype == torch.bfloat16), _ptr(status), _stream(rows)),
+                       "medtok_embed_sequence_rows_f16")
+    return res
+
+
+def _sequence_grad_args(fn, g, pad_mask, n_prefix):
+    """g floating [B, P + L, W] and pad_mask [B, L] of the sequence gradients -> (g fp32 contiguous on its device, pad_mask, B, L, W)"""
+    n_prefix = int(n_prefix)
+    if (not isinstance(g, torch.Tensor) or g.dtype not in EMBED_OUT_DTYPES or g.dim() != 3 or g.shape[2] < 1 or n_prefix < 0
+            or g.shape[1] < n_prefix):
+        raise ValueError(f"{fn}: g must be a floating [batch, {n_prefix} + length, width] tensor, got {getattr(g, 'dtype', type(g))} "
+                         f"{tuple(getattr(g, 'shape', ()))}")
+    batch, length, width = g.shape[0], g.shape[1] - n_prefix, g.shape[2]
+    if pad_mask is not None and (not isinstance(pad_mask, torch.Tensor) or pad_mask.dtype not in (torch.bool, torch.uint8)
+                                 or tuple(pad_mask.shape) != (batch, length)):
+        raise ValueError(f"{fn}: pad_mask must be a bool or uint8 [{batch}, {length}] tensor, got {getattr(pad_mask, 'dtype', type(pad_mask))} "
+                         f"{tuple(getattr(pad_mask, 'shape', ()))}")
+    if batch * (n_prefix + length) >= 1 << 31:
+        raise ValueError(f"{fn}: {batch} x ({n_prefix} + {length}) rows reach 2^31: split the batch")
+    return batch, length, width
+
+
+def embed_sequence_segment_grad(g, segment_id, n_segments, pad_mask=None, n_prefix=0):
+    """Gradient of embed_sequence's segment rows -> fp32 [B, V, W] (every segment term receives this tensor): G[b, v] = the sum of
+    g[b, P + p] over the unpadded p with segment_id[b, p] == v.  g floating [B, P + L, W] (a 16-bit one is converted to fp32 first:
+    exact); segment_id int64 [B, L]; pad_mask bool / uint8 [B, L].  Fixed order, no float atomics: per EMBED_SEQ_GRAD_CHUNK consecutive
+    positions of a batch row in ascending position order, then the chunk sums in chunk order -- two calls give the same bits.  Ids outside
+    [0, V) and padded positions contribute nothing.  V <= EMBED_SEQ_MAX_SEGMENTS.  Nothing is read back."""
+    fn = "embed_sequence_segment_grad"
+    batch, length, width = _sequence_grad_args(fn, g, pad_mask, n_prefix)
+    n_segments = int(n_segments)
+    if not 1 <= n_segments <= EMBED_SEQ_MAX_SEGMENTS:
+        raise ValueError(f"{fn}: V = {n_segments} segments unsupported (1 .. {EMBED_SEQ_MAX_SEGMENTS})")
+    if not isinstance(segment_id, torch.Tensor) or segment_id.dtype != torch.int64 or tuple(segment_id.shape) != (batch, length):
+        raise ValueError(f"{fn}: segment_id must be an int64 [{batch}, {length}] tensor, got {getattr(segment_id, 'dtype', type(segment_id))} "
+                         f"{tuple(getattr(segment_id, 'shape', ()))}")
+    if not g.is_cuda:
+        _dev(g, "g", g.dtype)
+    g = g.float().contiguous()
+    segment_id = _dev(segment_id, "segment_id", torch.int64)
+    pad_mask = _embed_mask_on_device(pad_mask)
+    out = torch.empty((batch, n_segments, width), dtype=torch.float32, device=g.device)
+    lib = _lib.load()
+    ws = _ws(lib.medtok_embed_sequence_grad_workspace_bytes(batch, length, n_segments, width), g)
+    with _on(g.device):
+        _lib.check(lib.medtok_embed_sequence_segment_grad_f32(g.data_ptr(), _ptr(pad_mask), segment_id.data_ptr(), batch, length, int(n_prefix),
+                                                              n_segments, width, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(g)),
+                   "medtok_embed_sequence_segment_grad_f32")
+    return out
+
+
+def embed_sequence_position_grad(g, n_rows, pad_mask=None, n_prefix=0):
+    """Gradient of embed_sequence's position rows -> fp32 [n_rows, W]: dpos[p] = the sum over b ascending of g[b, P + p] at the unpadded
+    (b, p) for p < L; the rows L <= p < n_rows (rows of the table the call did not use) are zeros.  g, pad_mask: as
+    embed_sequence_segment_grad.  Fixed order, no float atomics.  Nothing is read back."""
+    fn = "embed_sequence_position_grad"
+    batch, length, width = _sequence_grad_args(fn, g, pad_mask, n_prefix)
+    n_rows = int(n_rows)
+    if n_rows < length or n_rows >= 1 << 31:
+        raise ValueError(f"{fn}: n_rows = {n_rows} must be at least the {length} positions (and below 2^31)")
+    if not g.is_cuda:
+        _dev(g, "g", g.dtype)
+    g = g.float().contiguous()
+    pad_mask = _embed_mask_on_device(pad_mask)
+    out = torch.empty((n_rows, width), dtype=torch.float32, device=g.device)
+    lib = _lib.load()
+    with _on(g.device):
+        _lib.check(lib.medtok_embed_sequence_position_grad_f32(g.data_ptr(), _ptr(pad_mask), batch, length, int(n_prefix), width, n_rows,
+                                                               out.data_ptr(), _stream(g)), "medtok_embed_sequence_position_grad_f32")
+    return out
+
+
 def soft_vq_backward(x, xhat, what, idx, w, g_zq=None, g_xhat=None, g_out=None, g_vq=None, g_commit=None,
                      vq_scale: float = 0.0, commit_scale: float = 0.0, want_gx: bool = True, want_g_code: bool = True):
     """Sparse backward of the soft top-k assignment: (gx [n, d], g_code [n*k, d]).

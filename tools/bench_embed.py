@@ -54,6 +54,20 @@ frequencies are heavy-tailed); the gradients of codebook.weight are compared bef
 Per case also `peak_bytes`: the rise of torch.cuda.max_memory_allocated() over one forward + backward.  The result goes under the key
 "codebook_grad" of --out (the other keys are kept).
 
+--sequence H: the EHR model's input sequence (MedTokEmbedding.sequence: the folded lookup, a positional row per position, two time rows
+per position carried from its visit, three prefix rows in front; EHRModel_token.py:215-232) at the reference's own shape (MedTok_EHR.py:
+49,77-80) -- --batch 256 --length 2000, 100 visits, 3 prefix rows -- over the reference store shape, visits in ascending order along a
+row; compared before anything is timed (fp32: bit for bit at the unpadded positions and the prefix, the bias row at the padded ones):
+
+  sequence_f32 / _bf16       module.sequence(index, mask, position_rows=, segment_id=, segment_rows=[t0, t1], prefix=, validate=False)
+  composition_f32 / _bf16    what a user writes today: module(index, mask, validate=False) + pe[:L] + the two [B, L, H] gathers of the
+                             per-visit rows, added, torch.cat behind the prefix (bf16: converted at the end)
+  sequence_step / composition_step   forward + backward of the fp32 forms from a fixed upstream gradient, the additive tensors, the
+                             projector and miss_emb requiring gradients
+
+`spread` of a case = (ms_max - ms_min) / ms_median over its samples.  The result goes under the key "sequence" of --out (the other keys
+are kept).
+
 Discipline (bench_decode.py's): all sides are warmed up at the timed shape, compared before anything is timed, timed with device
 events over samples of >= 50 ms of back-to-back calls that ALTERNATE between the sides, at least 20 samples each; the shader clock
 (ops.ClockProbe) is read over further kernel samples right behind the timed region.  Algorithmic bytes of the kernel = per position
@@ -97,6 +111,9 @@ def main():
     ap.add_argument("--project", type=int, default=0, metavar="H", help="time the lookup with a folded nn.Linear(S * e_dim, H) instead")
     ap.add_argument("--pool", action="store_true", help="time bag pooling (MedTokEmbedding.pooled) instead")
     ap.add_argument("--codebook-grad", action="store_true", help="time forward + backward with freeze_codebook=False instead")
+    ap.add_argument("--sequence", type=int, default=0, metavar="H", help="time MedTokEmbedding.sequence against the torch composition instead")
+    ap.add_argument("--visits", type=int, default=100, help="--sequence: segments (visits) per batch row")
+    ap.add_argument("--prefix", type=int, default=3, help="--sequence: rows in front of each batch row")
     args = ap.parse_args()
     if args.reps < 20:
         ap.error("--reps must be at least 20")
@@ -130,6 +147,8 @@ def main():
         return pool_mode(args, dev, timed, stats)
     if args.codebook_grad:
         return codebook_grad_mode(args, dev, timed, inner_for, stats)
+    if args.sequence:
+        return sequence_mode(args, dev, timed, inner_for, stats)
 
     result = {"tool": "tools/bench_embed.py", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
               "num_codes": args.codes, "positions": [args.batch, args.length], "slots": 4, "k": args.k, "padded_fraction": args.padded,
@@ -570,6 +589,136 @@ def codebook_grad_mode(args, dev, timed, inner_for, stats):
         path = Path(args.out)
         whole = json.loads(path.read_text()) if path.exists() else {}
         whole["codebook_grad"] = result
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(whole, indent=1) + "\n")
+    print(json.dumps(result))
+
+
+def sequence_mode(args, dev, timed, inner_for, stats):
+    import torch
+    from medtok_amd import MedTokEmbedding, ops
+    from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer
+    h, n_seg, n_prefix = args.sequence, args.visits, args.prefix
+    batch, length = args.batch, args.length
+    name = "reference"
+    d, n_e = SHAPES[name]["d"], SHAPES[name]["n_e"]
+    k, num_codes, n_pos = args.k, args.codes, batch * length
+    torch.manual_seed(0)
+    vq = VectorQuantizer(n_e, d, 0.25, 0.0, True, False, [d, d], k=k)
+    with torch.no_grad():
+        vq.codebook.weight.normal_()
+    vq = vq.to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(1)
+    sizes = [hi - lo for lo, hi in (vq._region(t) for t in TYPES)]
+    tokens = torch.stack([torch.randint(0, s, (num_codes, k), generator=gen, device=dev) for s in sizes], 1).contiguous()
+    weights = torch.softmax(torch.randn(num_codes, 4, k, generator=gen, device=dev), -1).contiguous()
+    module = MedTokEmbedding(vq, tokens, weights, projector=torch.nn.Linear(4 * d, h).to(dev), fold=True)
+    del tokens, weights
+    index = torch.randint(0, num_codes, (batch, length), generator=gen, device=dev)
+    u = torch.rand(batch, length, generator=gen, device=dev)
+    index[u < args.miss] = num_codes
+    mask = u > 1.0 - args.padded
+    index[mask] = 0                                         # (the reference's dataloader pads with code 0 under its code_mask)
+    seg = torch.randint(0, n_seg, (batch, length), generator=gen, device=dev).sort(1).values      # visits in time order
+    rnd = lambda *shape: torch.randn(*shape, generator=gen, device=dev)
+    pe, t0, t1, prefix = rnd(length, h), rnd(batch, n_seg, h), rnd(batch, n_seg, h), rnd(batch, n_prefix, h)
+    g_out = rnd(batch, n_prefix + length, h)
+    gather_at = seg.unsqueeze(-1).expand(-1, -1, h)
+    leaves = [pe, t0, t1, prefix]
+    outs = {}
+
+    def sequence(dtype):
+        return module.sequence(index, mask, position_rows=pe, segment_id=seg, segment_rows=[t0, t1], prefix=prefix, validate=False, out_dtype=dtype)[0]
+
+    def composition():
+        x = module(index, padding_mask=mask, validate=False)
+        x = x + pe[:length]
+        x = x + t0.gather(1, gather_at)
+        x = x + t1.gather(1, gather_at)
+        return torch.cat([prefix, x], 1)
+
+    def sequence_f32():
+        with torch.no_grad():
+            outs["sequence_f32"] = sequence(torch.float32)
+
+    def sequence_bf16():
+        with torch.no_grad():
+            outs["sequence_bf16"] = sequence(torch.bfloat16)
+
+    def composition_f32():
+        with torch.no_grad():
+            outs["composition_f32"] = composition()
+
+    def composition_bf16():
+        with torch.no_grad():
+            outs["composition_bf16"] = composition().to(torch.bfloat16)
+
+    def step(fn):
+        module.zero_grad(set_to_none=True)
+        for t in leaves:
+            t.grad = None
+        fn().backward(g_out)
+
+    def sequence_step():
+        step(lambda: sequence(torch.float32))
+
+    def composition_step():
+        step(composition)
+
+    sides = {"sequence_f32": sequence_f32, "composition_f32": composition_f32, "sequence_bf16": sequence_bf16, "composition_bf16": composition_bf16}
+    for _ in range(args.warmup):
+        for fn in sides.values():
+            fn()
+    torch.cuda.synchronize()
+    live = ~mask
+    got, want = outs["sequence_f32"], outs["composition_f32"]
+    bias_rows = module.projector.bias.detach().expand(int(mask.sum()), -1)
+    equal = (torch.equal(got[:, :n_prefix], want[:, :n_prefix]) and torch.equal(got[:, n_prefix:][live], want[:, n_prefix:][live])
+             and torch.equal(got[:, n_prefix:][mask], bias_rows) and torch.equal(outs["sequence_bf16"], got.to(torch.bfloat16)))
+    if not equal:
+        raise SystemExit("sequence and the composition disagree at the timed size")
+    for t in leaves:
+        t.requires_grad_(True)
+    sides.update(sequence_step=sequence_step, composition_step=composition_step)
+    grads = {}
+    for _ in range(args.warmup):
+        for s in ("sequence_step", "composition_step"):
+            sides[s]()
+            grads[s] = [t.grad.clone() for t in leaves]
+    torch.cuda.synchronize()
+    # the composition's gradients also hold the padded positions' contributions (it adds there too) and come from atomics: reported, not asserted
+    grad_rel = [float((a - b).abs().max() / b.abs().max().clamp(min=1e-30)) for a, b in zip(grads["sequence_step"], grads["composition_step"])]
+    inner = {s: inner_for(fn) for s, fn in sides.items()}
+    ms = {s: [] for s in sides}
+    for _ in range(args.reps):                              # the sides alternate
+        for s, fn in sides.items():
+            ms[s].append(timed(fn, inner[s]))
+    with ops.ClockProbe(dev, max_seconds=10.0) as probe:
+        for _ in range(max(2, args.reps // 4)):
+            timed(sequence_f32, inner["sequence_f32"])
+    clock = probe.result()
+    st = {s: stats(v) for s, v in ms.items()}
+    rows, hp = module.fold_table_shape()
+    tensor_bytes = n_pos * h * 4
+    entry = {"d": d, "n_e": n_e, "k": k, "H": h, "num_codes": num_codes, "batch": batch, "length": length, "visits": n_seg, "prefix_rows": n_prefix,
+             "positions": n_pos, "live_positions": int((live & (index < num_codes)).sum()), "padded_fraction": args.padded,
+             "miss_fraction": args.miss, "table_rows": rows, "activation_bytes": tensor_bytes,
+             "outputs_bit_equal_fp32": equal, "step_grad_rel_vs_composition": dict(zip(("position_rows", "segment_rows0", "segment_rows1", "prefix"), grad_rel)),
+             "step_grad_note": "the composition adds the terms at padded positions too, so its gradients of the additive rows hold those positions' "
+                               "upstream rows as well: the two differ by design",
+             "clock_ghz": clock.get("ghz_mean"), "clock_region": "further sequence_f32 samples right behind the timed region"}
+    for s in sides:
+        entry[s] = dict(st[s], calls_per_sample=inner[s], spread=(st[s]["ms_max"] - st[s]["ms_min"]) / st[s]["ms_median"],
+                        positions_per_s=n_pos / (st[s]["ms_median"] * 1e-3))
+    for a, b in (("sequence_f32", "composition_f32"), ("sequence_bf16", "composition_bf16"), ("sequence_step", "composition_step")):
+        entry[f"{a}_speedup_over_composition"] = st[b]["ms_median"] / st[a]["ms_median"]
+        entry[f"{a}_not_slower_within_spread"] = st[a]["ms_median"] <= st[b]["ms_median"] + (st[b]["ms_max"] - st[b]["ms_min"])
+    result = {"tool": "tools/bench_embed.py --sequence", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
+              "shapes": {name: entry}}
+    if args.out:
+        path = Path(args.out)
+        whole = json.loads(path.read_text()) if path.exists() else {}
+        whole["sequence"] = result
         path.parent.mkdir(parents=True, exist_ok=True)
         path.write_text(json.dumps(whole, indent=1) + "\n")
     print(json.dumps(result))
