@@ -310,6 +310,30 @@ int medtok_embed_code_grad_f32(const float *g_out, int64_t g_stride, const int64
                                const int64_t *tokens, const float *weights, int64_t num_codes, int slots, int topk, int64_t n_codes, int d,
                                const int64_t *region_lo, const int64_t *region_size, float *g_what, float *bins, void *ws, size_t ws_bytes,
                                void *stream);
+/* The per-table-row sums of the upstream gradient of the FOLDED lookup (medtok_embed_project_* / medtok_embed_sequence_*): what both the
+ * projector's weight gradient (dW_s = G_s^T . what_s) and the codebook's gradient through the folded tables (d what[region s] += G_s . W_s)
+ * are made of, without the [n, slots * d] activation in either direction.  g [n, >= hp] (row stride g_stride in elements, 0 = hp, a
+ * multiple of 4; the rows aligned to four elements) in the type g_dtype names: a 16-bit g is read as 16-bit and widened in registers
+ * (exact), never copied to fp32.  hp % 4 == 0.  index, pad, tokens, weights, num_codes as medtok_embed_project_f32; row_offset / row_size
+ * (host arrays of `slots` entries) are its row_lo / row_size: slot s owns the rows [row_offset[s], + row_size[s]) of the folded table, and
+ * row_size[s] is also the range in which slot s's ids are valid.  G fp32 [table_rows, hp], bins fp32 [table_rows].
+ * Contribution ct = (p * slots + s) * topk + j is live by medtok_embed_code_grad_f32's rule (exactly when the forward mixes that
+ * (position, slot); a miss position contributes nothing), belongs to row row_offset[s] + tokens[index[p], s, j] and carries
+ * weights[index[p], s, j] * float(g[p, 0 : hp]) -- the WHOLE row of g, the same for every slot.  G[r] = the sum of the row's
+ * contributions, bins[r] their number, a row without any exactly zero.  The order is medtok_embed_code_grad_f32's and part of the result
+ * (increasing ct, one fmaf chain from +0 per MEDTOK_EMBED_CODE_GRAD_CHUNK contributions, the chunk sums added in chunk order): that entry
+ * gives the same bits on g tiled slots times.  No float atomics, nothing read back, no [n * slots, hp] buffer: the workspace is that
+ * entry's (16 bytes per contribution, 12 per table row, at most ceil(2 * n * slots * topk / CHUNK) chunk sums of hp floats), host
+ * arithmetic on the query's five arguments.  n * slots * topk >= 2^31, table_rows >= 2^31, hp % 4 != 0 (the query returns 0 for each)
+ * and a workspace that is too small are errors named as such, reported before any pointer is looked at and before anything is launched. */
+#define MEDTOK_EMBED_G_F32 0
+#define MEDTOK_EMBED_G_F16 1
+#define MEDTOK_EMBED_G_BF16 2
+size_t medtok_embed_table_grad_workspace_bytes(int64_t n, int slots, int topk, int64_t table_rows, int hp);
+int medtok_embed_table_grad(const void *g, int g_dtype, int64_t g_stride, const int64_t *index, const uint8_t *pad, int64_t n,
+                            const int64_t *tokens, const float *weights, int64_t num_codes, int slots, int topk, int64_t table_rows, int hp,
+                            const int64_t *row_offset, const int64_t *row_size, float *G, float *bins, void *ws, size_t ws_bytes,
+                            void *stream);
 /* Bag pooling: the normalised mean of a bag of codes in one pass (what the reference's QA adapter computes per sample in a Python loop
  * over the materialised table: gather, L2-normalise each row over its full width, mean over the set; review.py:50-64).  index
  * [bags, bag_len] int64, pad [bags, bag_len] or NULL (non-zero = padded, any pattern).  With row(p) the slots * d floats

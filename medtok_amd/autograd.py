@@ -659,7 +659,7 @@ class _EmbedProjectFunction(torch.autograd.Function):
                 chunk x S * d floats), dW += g_block^T . emb by the exact fp32 product;
       db        the column sum of g (padded positions are the bias row: they count);
       d miss    (sum of g over the unpadded miss positions, embed_codes_miss_grad at width H) . W.
-    A sorted per-code scatter form of dW (G_s^T . what_s over the folded tables' rows) is not built: DESIGN.md section 10."""
+    The scatter form of dW (G_s^T . what_s over the folded tables' rows) is _EmbedProjectScatterFunction."""
 
     @staticmethod
     def forward(ctx, w, b, miss, index, pad_mask, tokens, weights, what, regions, e_dim, folded, out_dtype, status):
@@ -708,6 +708,80 @@ def _embed_project_grads(g, w, miss, index, pad_mask, tokens, weights, what, reg
     return dw, db, dmiss
 
 
+def _embed_project_scatter_grads(g, w, miss, index, pad_mask, tokens, weights, what, regions, row_regions, e, has_bias, needs, weight=None):
+    """(dW, db, d miss, d codebook weight) of the folded lookup in the SCATTER form, from the upstream gradient g [n, Hp] (fp32, fp16 or
+    bf16) of its rows; needs: which of the four are wanted.  No [n, S * e] tensor exists: ops.embed_project_table_grad sums g per row of
+    the folded table in a fixed order, (G [rows, Hp], bins), and then, exact fp32 products (ops.small_gemm) throughout,
+      dW        dW[:, s * e : (s + 1) * e] = G_s^T . what[lo_s : lo_s + size_s, :e] per slot (2 * sum of sizes * e * H flops instead of
+                2 * n * S * e * H), plus the miss positions' outer product (sum of g over them) x miss_emb, which the dense form gets from
+                its recomputed rows;
+      db, d miss  as _embed_project_grads;
+      d weight  g_what = zeros; slots ascending: g_what[lo_s : lo_s + size_s] += G_s . W[:, s * e : (s + 1) * e] (zero columns appended
+                where the codebook is padded; two slots over one region add in slot order); live[r] = the bins of the slots that map to
+                codebook row r, summed; then F.normalize's backward, ops.normalize_backward(g_what, what, weight, live=live), as
+                _EmbedCodesTrainFunction finishes: rows no live contribution reaches are exactly zero.
+    Deterministic and without float atomics: two runs give the same bits."""
+    h, s, d = w.shape[0], len(regions), what.shape[1]
+    n = index.numel()
+    hp = ops.pad_dim(h)
+    g = g.reshape(n, hp)                                               # (the folded forward's rows are Hp wide; not -1: n may be 0)
+    index = index.reshape(-1)
+    pad_mask = None if pad_mask is None else pad_mask.reshape(-1)
+    wf = w.detach().float().contiguous()
+    dw = db = dmiss = dweight = None
+    want_w, want_b, want_miss, want_code = needs[0], has_bias and needs[1], miss is not None and needs[2], weight is not None and needs[3]
+    gf = g[:, :h].float().contiguous() if want_b or ((want_w or want_miss) and miss is not None) else None
+    g_rows = None
+    if gf is not None and miss is not None and (want_w or want_miss):
+        g_rows = ops.embed_codes_miss_grad(gf, index, tokens.shape[0], pad_mask) if n else gf.new_zeros(h)
+    if want_w or want_code:
+        G, bins = ops.embed_project_table_grad(g, index, tokens, weights, row_regions, pad_mask)
+    if want_w:
+        dw = torch.empty_like(wf)
+        for i, ((lo, size), (at, _)) in enumerate(zip(regions, row_regions)):
+            dw[:, i * e:(i + 1) * e] = ops.small_gemm(G[at:at + size], what[lo:lo + size, :e], trans_a=True)[:h]
+        if g_rows is not None:
+            dw.add_(ops.small_gemm(g_rows.view(h, 1), miss.detach().float().reshape(1, s * e)))
+    if want_b:
+        db = gf.sum(0)
+    if want_miss:
+        dmiss = ops.small_gemm(g_rows.view(1, h), wf).reshape(miss.shape)
+    if want_code:
+        wp = torch.nn.functional.pad(wf, (0, 0, 0, hp - h)) if hp != h else wf         # [Hp, S * e]: zero rows for the added columns
+        g_what = torch.zeros_like(what)
+        live = torch.zeros(what.shape[0], dtype=torch.float32, device=what.device)
+        for i, ((lo, size), (at, _)) in enumerate(zip(regions, row_regions)):
+            ws = wp[:, i * e:(i + 1) * e]
+            ws = torch.nn.functional.pad(ws, (0, d - e)) if d != e else ws.contiguous()
+            g_what[lo:lo + size].add_(ops.small_gemm(G[at:at + size], ws))
+            live[lo:lo + size].add_(bins[at:at + size])
+        dweight = ops.normalize_backward(g_what, what, weight.detach().float().contiguous(), live=live)
+    return dw, db, dmiss, dweight
+
+
+class _EmbedProjectScatterFunction(torch.autograd.Function):
+    """_EmbedProjectFunction with the scatter form of the backward (MedTokEmbedding(grad_form="scatter")) and one more differentiable
+    input, the codebook weight (padded to the normalised codebook's width; None where the codebook is frozen).  Forward: the same
+    kernel over the same folded tables, hence the same bits; the tables are folded from detached tensors, and this node's backward
+    supplies the codebook's gradient (_embed_project_scatter_grads).  A 16-bit upstream gradient goes to the sums as it is."""
+
+    @staticmethod
+    def forward(ctx, w, b, miss, weight, index, pad_mask, tokens, weights, what, regions, e_dim, folded, out_dtype, status):
+        table, row_regions, bias, miss_row = folded
+        out = ops.embed_project(index, tokens, weights, table, row_regions, bias, miss_row=miss_row, pad_mask=pad_mask, out_dtype=out_dtype,
+                                status=status)
+        ctx.save_for_backward(w, miss, weight, index, pad_mask, tokens, weights, what)
+        ctx.cfg = (tuple(regions), tuple(row_regions), int(e_dim), b is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        w, miss, weight, index, pad_mask, tokens, weights, what = ctx.saved_tensors
+        regions, row_regions, e, has_bias = ctx.cfg
+        return _embed_project_scatter_grads(g, w, miss, index, pad_mask, tokens, weights, what, regions, row_regions, e, has_bias,
+                                            ctx.needs_input_grad[:4], weight) + (None,) * 10
+
+
 def _sequence_part_grads(g, needs, n_rows, segment_id, n_segments, pad_mask, n_prefix):
     """(d position_rows, d segment_rows[0], d segment_rows[1], d prefix) from g fp32 [B, P + L, W]; needs: which of the four are wanted"""
     dpos = dseg = dprefix = None
@@ -754,6 +828,38 @@ class _EmbedSequenceFunction(torch.autograd.Function):
             grads = _embed_project_grads(g[:, n_prefix:].contiguous(), w, miss, index, pad_mask, tokens, weights, what, regions, e, has_bias,
                                          needs[:3])
         return grads + _sequence_part_grads(g, needs[3:7], n_rows, segment_id, n_segments, pad_mask, n_prefix) + (None,) * 11
+
+
+class _EmbedSequenceScatterFunction(torch.autograd.Function):
+    """_EmbedSequenceFunction with the scatter form of dW, db, d miss and the codebook's gradient (_embed_project_scatter_grads on a
+    contiguous copy of g[:, P:] in g's own dtype); the additive parts' gradients are _EmbedSequenceFunction's, from the fp32 g."""
+
+    @staticmethod
+    def forward(ctx, w, b, miss, weight, position_rows, seg0, seg1, prefix, index, pad_mask, segment_id, tokens, weights, what, regions, e_dim,
+                folded, out_dtype, status):
+        table, row_regions, bias, miss_row = folded
+        terms = tuple(t for t in (seg0, seg1) if t is not None)
+        out = ops.embed_sequence(index, tokens, weights, table, row_regions, bias, miss_row=miss_row, pad_mask=pad_mask,
+                                 position_rows=position_rows, segment_id=segment_id, segment_rows=terms or None, prefix=prefix, width=w.shape[0],
+                                 out_dtype=out_dtype, status=status)
+        ctx.save_for_backward(w, miss, weight, index, pad_mask, segment_id, tokens, weights, what)
+        ctx.cfg = (tuple(regions), tuple(row_regions), int(e_dim), b is not None, None if position_rows is None else position_rows.shape[0],
+                   0 if seg0 is None else seg0.shape[1], 0 if prefix is None else prefix.shape[1])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        w, miss, weight, index, pad_mask, segment_id, tokens, weights, what = ctx.saved_tensors
+        regions, row_regions, e, has_bias, n_rows, n_segments, n_prefix = ctx.cfg
+        needs = ctx.needs_input_grad
+        grads = (None, None, None, None)
+        if any(needs[:4]):
+            grads = _embed_project_scatter_grads(g[:, n_prefix:].contiguous(), w, miss, index, pad_mask, tokens, weights, what, regions,
+                                                 row_regions, e, has_bias, needs[:4], weight)
+        parts = (None, None, None, None)
+        if any(needs[4:8]):
+            parts = _sequence_part_grads(g[:, :, :w.shape[0]].float().contiguous(), needs[4:8], n_rows, segment_id, n_segments, pad_mask, n_prefix)
+        return grads + parts + (None,) * 11
 
 
 class _EmbedSequenceRowsFunction(torch.autograd.Function):

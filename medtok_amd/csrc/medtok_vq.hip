@@ -2530,6 +2530,35 @@ static bool code_grad_shape_ok(int64_t n, int slots, int topk, int64_t n_codes, 
            d > 0 && !(d & 3);
 }
 
+// What both gradients start with: the keys and their histogram, offsets[], first_chunk[] and the stable sort by row.  Returns which of
+// the two buffers holds the sorted payload.
+static int code_grad_sort(const CodeGradWs &w, const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, int64_t num_codes,
+                          int slots, int topk, const DecodeRegions &reg, int64_t n_codes, bool narrow, hipStream_t s)
+{
+    const long contributions = (long)n * slots * topk, items = (long)n * slots;
+    const int per = narrow ? 16 : 4;
+    hipLaunchKernelGGL(embed_code_grad_zero_kernel, dim3((unsigned)((n_codes + 255) / 256)), dim3(256), 0, s, w.counts, (long)n_codes);
+    if (narrow)
+        hipLaunchKernelGGL((embed_code_grad_keys_kernel<16>), dim3((unsigned)((items + per - 1) / per)), dim3(256), 0, s, index, pad, items, tokens,
+                           (long)num_codes, slots, topk, reg, (int)n_codes, w.keys[0], w.vals[0], w.counts);
+    else
+        hipLaunchKernelGGL((embed_code_grad_keys_kernel<64>), dim3((unsigned)((items + per - 1) / per)), dim3(256), 0, s, index, pad, items, tokens,
+                           (long)num_codes, slots, topk, reg, (int)n_codes, w.keys[0], w.vals[0], w.counts);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)n_codes, w.offsets);
+    hipLaunchKernelGGL(embed_code_grad_plan_kernel, dim3((unsigned)((n_codes + 255) / 256)), dim3(256), 0, s, w.counts, (long)n_codes);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)n_codes, w.first_chunk);
+    int cur = 0;
+    for (int shift = 0; shift == 0 || (n_codes >> shift); shift += 8) {       // keys lie in [0, n_codes]: the dead ones sort to the end
+        hipLaunchKernelGGL((radix_count_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], contributions,
+                           (int)n_codes, shift, w.wave_counts);
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.wave_counts, 256 * SORT_WAVES, w.wave_offsets);
+        hipLaunchKernelGGL((radix_scatter_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], w.vals[cur],
+                           contributions, (int)n_codes, shift, w.wave_offsets, w.keys[cur ^ 1], w.vals[cur ^ 1]);
+        cur ^= 1;
+    }
+    return cur;
+}
+
 extern "C" size_t medtok_embed_code_grad_workspace_bytes(int64_t n, int slots, int topk, int64_t n_codes, int d)
 {
     if (!code_grad_shape_ok(n, slots, topk, n_codes, d) || n > ((1ll << 31) - 1) / (slots * topk)) return 0;
@@ -2560,30 +2589,11 @@ extern "C" int medtok_embed_code_grad_f32(const float *g_out, int64_t g_stride, 
         return 0;
     }
     if (!g_out || !index || !tokens || !weights) return fail("%s: g_out, index, tokens and weights are required", fn);
-    const long contributions = (long)n * slots * topk, items = (long)n * slots;
-    CodeGradWs w = code_grad_ws_layout(ws, contributions, n_codes, d);
+    CodeGradWs w = code_grad_ws_layout(ws, (int64_t)n * slots * topk, n_codes, d);
     if (!ws || ws_bytes < w.total) return fail("%s: workspace too small (%zu < %zu)", fn, ws_bytes, w.total);
-    hipLaunchKernelGGL(embed_code_grad_zero_kernel, dim3((unsigned)((n_codes + 255) / 256)), dim3(256), 0, s, w.counts, (long)n_codes);
     const bool narrow = d <= 64;
     const int per = narrow ? 16 : 4;                              // items per block: 16 or 64 lanes each
-    if (narrow)
-        hipLaunchKernelGGL((embed_code_grad_keys_kernel<16>), dim3((unsigned)((items + per - 1) / per)), dim3(256), 0, s, index, pad, items, tokens,
-                           (long)num_codes, slots, topk, reg, (int)n_codes, w.keys[0], w.vals[0], w.counts);
-    else
-        hipLaunchKernelGGL((embed_code_grad_keys_kernel<64>), dim3((unsigned)((items + per - 1) / per)), dim3(256), 0, s, index, pad, items, tokens,
-                           (long)num_codes, slots, topk, reg, (int)n_codes, w.keys[0], w.vals[0], w.counts);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)n_codes, w.offsets);
-    hipLaunchKernelGGL(embed_code_grad_plan_kernel, dim3((unsigned)((n_codes + 255) / 256)), dim3(256), 0, s, w.counts, (long)n_codes);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)n_codes, w.first_chunk);
-    int cur = 0;
-    for (int shift = 0; shift == 0 || (n_codes >> shift); shift += 8) {       // keys lie in [0, n_codes]: the dead ones sort to the end
-        hipLaunchKernelGGL((radix_count_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], contributions,
-                           (int)n_codes, shift, w.wave_counts);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.wave_counts, 256 * SORT_WAVES, w.wave_offsets);
-        hipLaunchKernelGGL((radix_scatter_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], w.vals[cur],
-                           contributions, (int)n_codes, shift, w.wave_offsets, w.keys[cur ^ 1], w.vals[cur ^ 1]);
-        cur ^= 1;
-    }
+    const int cur = code_grad_sort(w, index, pad, n, tokens, num_codes, slots, topk, reg, n_codes, narrow, s);
     const long work = (long)n_codes + w.extra;
     if (narrow)
         hipLaunchKernelGGL((embed_code_grad_chunk_kernel<16>), dim3((unsigned)((work + per - 1) / per)), dim3(256), 0, s, g_out, (long)g_stride, index,
@@ -2595,6 +2605,70 @@ extern "C" int medtok_embed_code_grad_f32(const float *g_out, int64_t g_stride, 
                            w.chunk_sums);
     hipLaunchKernelGGL(embed_code_grad_combine_kernel, dim3((unsigned)lmin(4096, (n_codes + 3) / 4)), dim3(256), 0, s, w.chunk_sums, w.first_chunk,
                        (long)n_codes, d, g_what);
+    return check_launch(fn);
+}
+
+// ---- per-table-row sums of the folded lookup's upstream gradient (embed_table_grad_kernels.h): the same keys, sort, plan and combine
+#include "embed_table_grad_kernels.h"
+
+extern "C" size_t medtok_embed_table_grad_workspace_bytes(int64_t n, int slots, int topk, int64_t table_rows, int hp)
+{
+    if (!code_grad_shape_ok(n, slots, topk, table_rows, hp) || n > ((1ll << 31) - 1) / (slots * topk)) return 0;
+    return code_grad_ws_layout(nullptr, n * slots * topk, table_rows, hp).total;
+}
+
+template <int LANES, typename G_T>
+static void table_grad_chunks(const void *g, int64_t g_stride, const int64_t *index, const float *weights, int64_t num_codes, int slots, int topk,
+                              int hp, const CodeGradWs &w, int cur, int64_t table_rows, float *bins, float *G, hipStream_t s)
+{
+    const int per = 256 / LANES;
+    const long work = (long)table_rows + w.extra;
+    hipLaunchKernelGGL((embed_table_grad_chunk_kernel<LANES, G_T>), dim3((unsigned)((work + per - 1) / per)), dim3(256), 0, s, (const G_T *)g,
+                       (long)g_stride, index, weights, (long)num_codes, slots, topk, hp, w.vals[cur], w.offsets, w.first_chunk, (long)table_rows,
+                       w.extra, bins, G, w.chunk_sums);
+}
+
+extern "C" int medtok_embed_table_grad(const void *g, int g_dtype, int64_t g_stride, const int64_t *index, const uint8_t *pad, int64_t n,
+                                       const int64_t *tokens, const float *weights, int64_t num_codes, int slots, int topk, int64_t table_rows,
+                                       int hp, const int64_t *row_offset, const int64_t *row_size, float *G, float *bins, void *ws,
+                                       size_t ws_bytes, void *stream)
+{
+    const char *fn = "embed_table_grad";
+    if (hp > 0 && (hp & 3)) return fail("%s: hp=%d is not a multiple of 4", fn, hp);
+    if (table_rows >= (1ll << 31)) return fail("%s: table_rows = %ld reach 2^31 (the sort's keys are 32-bit)", fn, (long)table_rows);
+    if (!code_grad_shape_ok(n, slots, topk, table_rows, hp))
+        return fail("%s: bad shape n=%ld slots=%d topk=%d table_rows=%ld hp=%d", fn, (long)n, slots, topk, (long)table_rows, hp);
+    if (n > ((1ll << 31) - 1) / (slots * topk))
+        return fail("%s: n * slots * topk = %ld x %d x %d contributions reach 2^31 (the sort's payload is 32-bit): split the batch", fn, (long)n,
+                    slots, topk);
+    if (g_dtype != MEDTOK_EMBED_G_F32 && g_dtype != MEDTOK_EMBED_G_F16 && g_dtype != MEDTOK_EMBED_G_BF16)
+        return fail("%s: g_dtype=%d unsupported (MEDTOK_EMBED_G_F32, _F16 or _BF16)", fn, g_dtype);
+    const CodeGradWs need = code_grad_ws_layout(nullptr, (int64_t)n * slots * topk, table_rows, hp);
+    if (n > 0 && ws_bytes < need.total) return fail("%s: workspace too small (%zu < %zu)", fn, ws_bytes, need.total);
+    DecodeRegions reg;
+    if (int rc = decode_args(fn, n, slots, topk, table_rows, hp, row_offset, row_size, reg)) return rc;
+    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
+    if (g_stride == 0) g_stride = hp;
+    if (g_stride < hp || (g_stride & 3)) return fail("%s: g_stride must be >= hp and a multiple of 4", fn);
+    if (!G || !bins) return fail("%s: G and bins are required", fn);
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        if (hipMemsetAsync(G, 0, (size_t)table_rows * hp * sizeof(float), s) != hipSuccess || hipMemsetAsync(bins, 0, (size_t)table_rows * sizeof(float), s) != hipSuccess)
+            return fail("%s: memset failed", fn);
+        return 0;
+    }
+    if (!g || !index || !tokens || !weights || !ws) return fail("%s: g, index, tokens, weights and ws are required", fn);
+    if (((uintptr_t)g & (g_dtype == MEDTOK_EMBED_G_F32 ? 15 : 7))) return fail("%s: g must be aligned to four of its elements", fn);
+    const CodeGradWs w = code_grad_ws_layout(ws, (int64_t)n * slots * topk, table_rows, hp);
+    const bool narrow = hp <= 64;
+    const int cur = code_grad_sort(w, index, pad, n, tokens, num_codes, slots, topk, reg, table_rows, narrow, s);
+#define MEDTOK_TABLE_GRAD(L, T) table_grad_chunks<L, T>(g, g_stride, index, weights, num_codes, slots, topk, hp, w, cur, table_rows, bins, G, s)
+    if (g_dtype == MEDTOK_EMBED_G_F32) { if (narrow) MEDTOK_TABLE_GRAD(16, float); else MEDTOK_TABLE_GRAD(64, float); }
+    else if (g_dtype == MEDTOK_EMBED_G_F16) { if (narrow) MEDTOK_TABLE_GRAD(16, _Float16); else MEDTOK_TABLE_GRAD(64, _Float16); }
+    else { if (narrow) MEDTOK_TABLE_GRAD(16, __bf16); else MEDTOK_TABLE_GRAD(64, __bf16); }
+#undef MEDTOK_TABLE_GRAD
+    hipLaunchKernelGGL(embed_code_grad_combine_kernel, dim3((unsigned)lmin(4096, (table_rows + 3) / 4)), dim3(256), 0, s, w.chunk_sums, w.first_chunk,
+                       (long)table_rows, hp, G);
     return check_launch(fn);
 }
 

@@ -23,8 +23,9 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import (_EmbedCodesFunction, _EmbedCodesTrainFunction, _EmbedPoolFunction, _EmbedProjectFunction, _EmbedSequenceFunction,
-                       _EmbedSequenceRowsFunction, small_linear)
+from .autograd import (_EmbedCodesFunction, _EmbedCodesTrainFunction, _EmbedPoolFunction, _EmbedProjectFunction,
+                       _EmbedProjectScatterFunction, _EmbedSequenceFunction, _EmbedSequenceRowsFunction, _EmbedSequenceScatterFunction,
+                       small_linear)
 
 DEFAULT_TYPES = ("text", "graph", "shared", "shared")
 
@@ -61,7 +62,18 @@ class MedTokEmbedding(nn.Module):
     counts how often they were built.  The quantizer caches its normalised codebook in eval mode only: while it is in train() mode
     (e.g. as a submodule of a model that was sent .train()) every call normalises afresh, so the key changes and the tables are
     refolded on every call, and fold=None never sees a valid cache; keep a frozen quantizer in eval().  Without a projector nothing
-    here changes."""
+    here changes.
+
+    grad_form: how a call that takes the folded route is differentiated.  "dense" (the default) recomputes the embeddings in blocks and
+    multiplies them with the upstream gradient (autograd._embed_project_grads), and a codebook that trains (freeze_codebook=False)
+    switches the fold off.  "scatter" sums the upstream rows per row of the folded tables in a fixed order
+    (ops.embed_project_table_grad: a sort of 8 bytes per contribution, no float atomics, nothing read back) and takes dW = G_s^T . what_s
+    and the codebook's gradient G_s . W_s from those sums: no [positions, S * e_dim] tensor exists in either direction, and
+    freeze_codebook=False no longer forces fold=False (fold=True folds, fold=None applies fold_rule; the tables are refolded per
+    weight version as said above, i.e. once per optimiser step with the quantizer in eval()).  The forward is the same kernel over the
+    same tables in both forms, hence the same bits; where the folded route is not taken (fold_rule says no, fold=False, or a training
+    codebook with e_dim % 4 != 0) nothing changes, and `pooled` is untouched.  The default stays "dense" until the measurement of
+    DESIGN.md section 7.1h is in; flipping it is a separate change."""
 
     # The memory budget of the folded tables (sum of the slots' region sizes x H rounded up to 4 x 4 bytes; 134 MB for a 256-wide
     # projector over cfg 3's 49,152 codes): above it fold=None takes the lookup followed by the dense product.  Chosen by size alone:
@@ -71,7 +83,7 @@ class MedTokEmbedding(nn.Module):
     FOLD_COLD_FACTOR = 3
 
     def __init__(self, quantizer, tokens, weights, types=DEFAULT_TYPES, miss_row: bool = True, freeze_codebook: bool = True,
-                 global_ids: bool = False, projector=None, fold=None):
+                 global_ids: bool = False, projector=None, fold=None, grad_form: str = "dense"):
         super().__init__()
         kinds = (types,) if isinstance(types, str) else tuple(types)
         if not 1 <= len(kinds) <= ops.DECODE_MAX_SLOTS or any(t not in quantizer.DECODE_TYPES for t in kinds):
@@ -106,6 +118,11 @@ class MedTokEmbedding(nn.Module):
             raise ValueError(f"MedTokEmbedding: fold must be None, True or False, got {fold!r}")
         if fold is not None and projector is None:
             raise ValueError(f"MedTokEmbedding: fold={fold!r} without a projector: there is nothing to fold")
+        if grad_form not in ("dense", "scatter"):
+            raise ValueError(f"MedTokEmbedding: grad_form must be 'dense' or 'scatter', got {grad_form!r}")
+        if grad_form == "scatter" and projector is None:
+            raise ValueError("MedTokEmbedding: grad_form='scatter' without a projector: only the folded route has a scatter form")
+        self.grad_form = grad_form
         if projector is not None:
             if not isinstance(projector, nn.Linear) or projector.in_features != self.embedding_dim:
                 raise ValueError(f"MedTokEmbedding: projector must be an nn.Linear with in_features = S * e_dim = {self.embedding_dim}, got "
@@ -261,15 +278,21 @@ class MedTokEmbedding(nn.Module):
             if p.weight.dtype != torch.float32:
                 raise ValueError(f"MedTokEmbedding: the projector must be fp32 (every product behind the lookup is), got {p.weight.dtype}")
             want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
-            norm = None if want_codebook else q._normalised_codebook()
-            fold = False if want_codebook else self.fold
+            unfolded = want_codebook and not self._scatter_trains()
+            norm = None if unfolded else q._normalised_codebook()
+            fold = False if unfolded else self.fold
             if fold is None:
                 cache = self._fold_cache
                 fold = self.fold_rule(index.numel(), cache is not None and cache[0] == self._fold_key(norm))
         status = torch.zeros(1, dtype=torch.int32, device=dev) if validate else None
         if fold:
             folded = self._folded(norm)
-            if parts_grad or (grad_on and any(t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb))):
+            if self.grad_form == "scatter" and (parts_grad or want_codebook or (grad_on and any(
+                    t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb)))):
+                seq = _EmbedSequenceScatterFunction.apply(p.weight, p.bias, self.miss_emb, self._codebook_input() if want_codebook else None,
+                                                          position_rows, seg0, seg1, prefix, index, padding_mask, segment_id, self.tokens,
+                                                          self.weights, norm[0], tuple(regions), int(q.e_dim), folded, out_dtype, status)
+            elif parts_grad or (grad_on and any(t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb))):
                 seq = _EmbedSequenceFunction.apply(p.weight, p.bias, self.miss_emb, position_rows, seg0, seg1, prefix, index, padding_mask,
                                                    segment_id, self.tokens, self.weights, norm[0], tuple(regions), int(q.e_dim), folded, out_dtype,
                                                    status)
@@ -385,6 +408,14 @@ class MedTokEmbedding(nn.Module):
             return False
         return bool(cache_valid) or positions * len(self.types) >= self.FOLD_COLD_FACTOR * rows
 
+    def _scatter_trains(self):
+        """whether a codebook that trains may stay on the folded route: grad_form="scatter" (e_dim % 4 != 0 keeps the unfolded route)"""
+        return self.grad_form == "scatter" and not getattr(self.quantizer, "_pad", 0)
+
+    def _codebook_input(self):
+        """codebook.weight as the scatter nodes take it: fp32, under autograd"""
+        return self.quantizer.codebook.weight.float()
+
     def _fold_key(self, norm):
         tensors = (self.projector.weight, self.projector.bias, self.miss_emb)
         return (id(norm),) + tuple(None if t is None else (t._version, t.data_ptr(), t.device) for t in tensors)
@@ -412,8 +443,9 @@ class MedTokEmbedding(nn.Module):
         padding_mask, out_dtype = self._checked(index, padding_mask, out_dtype, out, h)
         grad_on = out is None and torch.is_grad_enabled()
         want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
-        norm = None if want_codebook else q._normalised_codebook()
-        fold = False if want_codebook else self.fold
+        unfolded = want_codebook and not self._scatter_trains()
+        norm = None if unfolded else q._normalised_codebook()
+        fold = False if unfolded else self.fold
         if fold is None:
             cache = self._fold_cache
             fold = self.fold_rule(n, cache is not None and cache[0] == self._fold_key(norm))
@@ -430,7 +462,11 @@ class MedTokEmbedding(nn.Module):
         regions = self._regions()
         status = torch.zeros(1, dtype=torch.int32, device=self.tokens.device) if validate else None
         wants = [t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb)]
-        if grad_on and any(wants):
+        if self.grad_form == "scatter" and grad_on and (any(wants) or want_codebook):
+            res = _EmbedProjectScatterFunction.apply(p.weight, p.bias, self.miss_emb, self._codebook_input() if want_codebook else None, index,
+                                                     padding_mask, self.tokens, self.weights, norm[0], tuple(regions), int(q.e_dim), folded,
+                                                     out_dtype, status)
+        elif grad_on and any(wants):
             res = _EmbedProjectFunction.apply(p.weight, p.bias, self.miss_emb, index, padding_mask, self.tokens, self.weights, norm[0],
                                               tuple(regions), int(q.e_dim), folded, out_dtype, status)
         else:

@@ -512,6 +512,71 @@ def embed_codes_code_grad(g_out, index, tokens, weights, what_shape_or_what, reg
     return g_what, bins
 
 
+EMBED_G_DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}       # MEDTOK_EMBED_G_F32 / _F16 / _BF16
+
+
+def embed_project_table_grad(g, index, tokens, weights, row_regions, pad_mask=None):
+    """The upstream gradient of embed_project / embed_sequence's rows summed per row of the folded table -> (G [rows, Hp], bins [rows]),
+    rows = the end of the last region.
+
+    g [*index.shape, Hp], fp32, fp16 or bf16 (a 16-bit g goes to the kernel as it is and is widened in registers: exact), Hp % 4 == 0;
+    a view with unit column stride and 16-byte aligned rows (a column block of a wider tensor) is read in place, anything else is made
+    contiguous.  index, tokens, weights, pad_mask as embed_project; row_regions [(offset, size)] per slot as fold_projector returned
+    them (size is also the range of the slot's ids; regions may coincide).  Contribution (p, s, j) is live exactly when the forward
+    mixes that (position, slot) -- embed_codes_code_grad's rule; a miss position contributes nothing -- and adds
+    weights[index[p], s, j] * g[p] (the whole row, the same for every slot) to row offset_s + tokens[index[p], s, j]; bins counts a row's
+    live contributions, a row without any is exactly zero.  Order and chunking are embed_codes_code_grad's (EMBED_CODE_GRAD_CHUNK): that
+    function gives the same bits on g tiled S times.  No float atomics, no [n * S, Hp] buffer, nothing read back.
+    dW[:, s * e : (s + 1) * e] = G_s^T . what[region s] and d what[region s] += G_s . W_s follow by small_gemm."""
+    fn = "embed_project_table_grad"
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+    pad_mask = _embed_mask(fn, pad_mask, index)
+    n = index.numel()
+    if (not isinstance(g, torch.Tensor) or g.dtype not in EMBED_G_DTYPE_CODES or g.dim() < 1 or g.shape[-1] < 1 or g.shape[-1] % 4
+            or g.numel() != n * g.shape[-1]):
+        raise ValueError(f"{fn}: g must be an fp32, fp16 or bf16 [*{tuple(index.shape)}, Hp] tensor with Hp % 4 == 0, got "
+                         f"{getattr(g, 'dtype', type(g))} {tuple(getattr(g, 'shape', ()))}")
+    hp = int(g.shape[-1])
+    try:
+        row_regions = [(int(lo), int(size)) for lo, size in row_regions]
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: row_regions must be a sequence of (offset, size) pairs, got {row_regions!r}") from None
+    if not row_regions or any(lo < 0 or size < 1 for lo, size in row_regions):
+        raise ValueError(f"{fn}: every region needs offset >= 0 and size >= 1, got {row_regions}")
+    rows = max(lo + size for lo, size in row_regions)
+    if rows >= 1 << 31:
+        raise ValueError(f"{fn}: {rows} table rows reach 2^31 (the sort's keys are 32-bit)")
+    table = torch.empty((rows, hp), dtype=torch.float32, device="meta")          # (shape checks only: no storage)
+    tokens, weights, row_regions = _decode_shapes(fn, tokens, weights, table, row_regions)
+    num_codes, s, k = tokens.shape
+    if num_codes < 1:
+        raise ValueError(f"{fn}: the token table is empty")
+    if n * s * k >= 1 << 31:
+        raise ValueError(f"{fn}: {n} positions x {s} slots x {k} ids reach 2^31 contributions (the sort's payload is 32-bit): split the batch")
+    index = _dev(index, "index", torch.int64)
+    tokens, weights = _dev(tokens, "tokens", torch.int64), _dev(weights, "weights")
+    pad_mask = _embed_mask_on_device(pad_mask)
+    if not g.is_cuda:
+        _dev(g, "g", g.dtype)
+    g = g.reshape(n, hp)
+    if n and not (g.stride(1) == 1 and g.stride(0) >= hp and g.stride(0) * g.element_size() % 16 == 0 and g.data_ptr() % 16 == 0):
+        g = g.contiguous()
+    import ctypes as C
+    arr = C.c_int64 * s
+    los, sizes = arr(*[r[0] for r in row_regions]), arr(*[r[1] for r in row_regions])
+    lib = _lib.load()
+    dev = g.device
+    G = torch.empty((rows, hp), dtype=torch.float32, device=dev)
+    bins = torch.empty(rows, dtype=torch.float32, device=dev)
+    ws = _ws(lib.medtok_embed_table_grad_workspace_bytes(n, s, k, rows, hp), g)
+    with _on(dev):
+        _lib.check(lib.medtok_embed_table_grad(g.data_ptr(), EMBED_G_DTYPE_CODES[g.dtype], g.stride(0) if n else 0, index.data_ptr(), _ptr(pad_mask), n,
+                                               tokens.data_ptr(), weights.data_ptr(), num_codes, s, k, rows, hp, los, sizes, G.data_ptr(),
+                                               bins.data_ptr(), ws.data_ptr(), ws.numel(), _stream(g)), "medtok_embed_table_grad")
+    return G, bins
+
+
 EMBED_POOL_CHUNK = 16                       # positions per block of embed_pool_partial_kernel (MEDTOK_EMBED_POOL_CHUNK: part of the result's bits)
 EMBED_POOL_MAX_WIDTH = 4096
 

@@ -68,6 +68,23 @@ row; compared before anything is timed (fp32: bit for bit at the unpadded positi
 `spread` of a case = (ms_max - ms_min) / ms_median over its samples.  The result goes under the key "sequence" of --out (the other keys
 are kept).
 
+--grad-form (with --project H or --sequence H): forward + backward of the folded route with MedTokEmbedding(grad_form="scatter") against
+grad_form="dense" (the parent commit's arithmetic unchanged), both modules over one projector and one miss row, from a fixed upstream
+gradient; outputs (bit for bit) and gradients (1e-5 of their scale between the sides; dW, whose entries sum over every position, 1e-4
+of its fp64 restatement on both sides, both errors recorded) are compared at the timed size before anything is timed:
+
+  --project H --grad-form                    frozen codebook, fold=True on both sides, the two workloads of --project
+  --sequence H --grad-form                   the --sequence step (--batch 256 --length 2000), the additive tensors requiring gradients too
+  --project H --grad-form --train-codebook   freeze_codebook=False: scatter stays folded, dense unfolds (the lookup's [n, S * e_dim] rows and
+                                             small_linear); a random store and the "hot" store of --codebook-grad per workload; a third
+                                             side, scatter_refold, drops the cached tables before every step (what a step that
+                                             follows an optimiser step pays)
+
+Per side the timing statistics, `spread` and `peak_bytes` (the rise of torch.cuda.max_memory_allocated() over one step); per case
+`table_grad_ms`, ops.embed_project_table_grad alone on the same upstream gradient (its sort and its sums are not separated: that takes
+a kernel trace), and `scatter_not_slower_within_dense_spread`: scatter's median <= dense's median + (dense's max - dense's min).  The
+result goes under the key "table_grad" of --out, one sub-key per invocation form (the other keys are kept).
+
 Discipline (bench_decode.py's): all sides are warmed up at the timed shape, compared before anything is timed, timed with device
 events over samples of >= 50 ms of back-to-back calls that ALTERNATE between the sides, at least 20 samples each; the shader clock
 (ops.ClockProbe) is read over further kernel samples right behind the timed region.  Algorithmic bytes of the kernel = per position
@@ -114,6 +131,8 @@ def main():
     ap.add_argument("--sequence", type=int, default=0, metavar="H", help="time MedTokEmbedding.sequence against the torch composition instead")
     ap.add_argument("--visits", type=int, default=100, help="--sequence: segments (visits) per batch row")
     ap.add_argument("--prefix", type=int, default=3, help="--sequence: rows in front of each batch row")
+    ap.add_argument("--grad-form", action="store_true", help="with --project / --sequence: time grad_form='scatter' against 'dense' instead")
+    ap.add_argument("--train-codebook", action="store_true", help="--project H --grad-form: with freeze_codebook=False")
     args = ap.parse_args()
     if args.reps < 20:
         ap.error("--reps must be at least 20")
@@ -141,6 +160,10 @@ def main():
     def stats(ms):
         return dict(ms_median=statistics.median(ms), ms_min=min(ms), ms_max=max(ms), ms_mean=statistics.fmean(ms), samples=len(ms))
 
+    if args.grad_form:
+        if not (args.project or args.sequence) or (args.train_codebook and not args.project):
+            ap.error("--grad-form goes with --project H or --sequence H; --train-codebook with --project H")
+        return grad_form_mode(args, dev, timed, inner_for, stats)
     if args.project:
         return project_mode(args, dev, timed, inner_for, stats)
     if args.pool:
@@ -719,6 +742,154 @@ def sequence_mode(args, dev, timed, inner_for, stats):
         path = Path(args.out)
         whole = json.loads(path.read_text()) if path.exists() else {}
         whole["sequence"] = result
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(whole, indent=1) + "\n")
+    print(json.dumps(result))
+
+
+def grad_form_mode(args, dev, timed, inner_for, stats):
+    import torch
+    from medtok_amd import MedTokEmbedding, ops
+    from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer
+    seq, train = bool(args.sequence), args.train_codebook
+    h = args.sequence or args.project
+    form = "sequence" if seq else "project_training" if train else "project_frozen"
+    batch, length, k, num_codes, n_pos = args.batch, args.length, args.k, args.codes, args.batch * args.length
+    result = {"tool": f"tools/bench_embed.py --{'sequence' if seq else 'project'} {h} --grad-form" + (" --train-codebook" if train else ""),
+              "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0), "num_codes": num_codes,
+              "positions": [batch, length], "slots": 4, "k": k, "H": h, "padded_fraction": args.padded, "miss_fraction": args.miss,
+              "chunk": ops.EMBED_CODE_GRAD_CHUNK, "cases": {}}
+    for name in (["reference"] if seq else args.shapes.split(",")):
+        d, n_e = SHAPES[name]["d"], SHAPES[name]["n_e"]
+        torch.manual_seed(0)
+        vq = VectorQuantizer(n_e, d, 0.25, 0.0, True, False, [d, d], k=k)
+        with torch.no_grad():
+            vq.codebook.weight.normal_()
+        vq = vq.to(dev).eval()
+        gen = torch.Generator(device=dev).manual_seed(1)
+        sizes = [hi - lo for lo, hi in (vq._region(t) for t in TYPES)]
+        tokens = torch.stack([torch.randint(0, s, (num_codes, k), generator=gen, device=dev) for s in sizes], 1).contiguous()
+        weights = torch.softmax(torch.randn(num_codes, 4, k, generator=gen, device=dev), -1).contiguous()
+        proj = torch.nn.Linear(4 * d, h).to(dev)
+        kw = dict(projector=proj, fold=True, freeze_codebook=not train)
+        mods = {"scatter": MedTokEmbedding(vq, tokens, weights, grad_form="scatter", **kw)}
+        mods["dense"] = MedTokEmbedding(vq, tokens, weights, grad_form="dense", **kw)
+        mods["dense"].tokens, mods["dense"].weights, mods["dense"].miss_emb = mods["scatter"].tokens, mods["scatter"].weights, mods["scatter"].miss_emb
+        plain = MedTokEmbedding(vq, tokens, weights)            # (the fp64 restatement of dW takes its rows from the lookup kernel)
+        plain.tokens, plain.weights, plain.miss_emb = mods["scatter"].tokens, mods["scatter"].weights, mods["scatter"].miss_emb
+        del tokens, weights
+        rnd = lambda *shape: torch.randn(*shape, generator=gen, device=dev)
+        n_prefix = args.prefix if seq else 0
+        g_out = rnd(batch, n_prefix + length, h)
+        leaves = []
+        if seq:
+            seg = torch.randint(0, args.visits, (batch, length), generator=gen, device=dev).sort(1).values
+            leaves = [rnd(length, h), rnd(batch, args.visits, h), rnd(batch, args.visits, h), rnd(batch, n_prefix, h)]
+            for t in leaves:
+                t.requires_grad_(True)
+        params = [proj.weight, proj.bias, mods["scatter"].miss_emb] + ([vq.codebook.weight] if train else [])
+        for variant in (("random", "hot") if train else ("random",)):
+            index = torch.randint(0, num_codes, (batch, length), generator=gen, device=dev)
+            u = torch.rand(batch, length, generator=gen, device=dev)
+            if variant == "hot":                                # half the live positions on one code
+                index[torch.rand(batch, length, generator=gen, device=dev) < 0.5] = 7
+            index[u < args.miss] = num_codes
+            mask = u > 1.0 - args.padded
+            index[mask] = 0
+            outs, grads = {}, {}
+
+            def step(side):
+                m = mods[side]
+                for t in params + leaves:
+                    t.grad = None
+                if seq:
+                    out = m.sequence(index, mask, position_rows=leaves[0], segment_id=seg, segment_rows=leaves[1:3], prefix=leaves[3], validate=False)[0]
+                else:
+                    out = m(index, padding_mask=mask, validate=False)
+                out.backward(g_out)
+                outs[side] = out.detach()
+                grads[side] = [t.grad for t in params + leaves]
+
+            def scatter_refold():                               # what a step after an optimiser step pays: the tables folded again
+                mods["scatter"].__dict__["_fold_cache"] = None
+                step("scatter")
+
+            sides = {"scatter": lambda: step("scatter"), "dense": lambda: step("dense")}
+            if train:
+                sides["scatter_refold"] = scatter_refold
+            peak = {}
+            for _ in range(args.warmup):
+                for s, fn in sides.items():
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    before = torch.cuda.memory_allocated()
+                    fn()
+                    torch.cuda.synchronize()
+                    peak[s] = torch.cuda.max_memory_allocated() - before
+            out_rel = float((outs["scatter"] - outs["dense"]).abs().max() / outs["dense"].abs().max())
+            if not (out_rel <= 1e-5 and (train or torch.equal(outs["scatter"], outs["dense"]))):
+                raise SystemExit(f"{name}/{variant}: the outputs of the two forms disagree (rel {out_rel})")
+            names = ["dW", "db", "d_miss"] + (["d_codebook"] if train else []) + (["d_position_rows", "d_segment_rows0", "d_segment_rows1", "d_prefix"] if seq else [])
+            grad_rel = {nm: float((a - b).abs().max() / b.abs().max().clamp(min=1e-30)) for nm, a, b in zip(names, grads["scatter"], grads["dense"])}
+            # dW against its fp64 restatement g^T . emb (emb: the lookup kernel's fp32 rows).  An entry of dW sums up to n_pos products, in
+            # two different fp32 orders on the two sides: their rounding alone reaches sqrt(n_pos) * 2^-24 ~ 2e-5 to 4e-5 of the scale
+            # at these sizes, so dW is held to 1e-4 of the fp64 result (a wrong gradient is off by order 1) and both errors are
+            # recorded; every other gradient is held to 1e-5 between the sides.
+            with torch.no_grad():
+                dw64 = torch.zeros(h, 4 * d, dtype=torch.float64, device=dev)
+                flat_i, flat_m, flat_g = index.reshape(-1), mask.reshape(-1), g_out[:, n_prefix:].reshape(n_pos, h)
+                for r0 in range(0, n_pos, 32768):
+                    emb = plain(flat_i[r0:r0 + 32768], padding_mask=flat_m[r0:r0 + 32768], validate=False).double()
+                    dw64 += flat_g[r0:r0 + 32768].double().t() @ emb
+                dw_rel64 = {s: float((grads[s][0] - dw64).abs().max() / dw64.abs().max()) for s in ("scatter", "dense")}
+                del dw64, emb
+            if not max(v for nm, v in grad_rel.items() if nm != "dW") <= 1e-5 or not max(dw_rel64.values()) <= 1e-4:
+                raise SystemExit(f"{name}/{variant}: the gradients of the two forms disagree: {grad_rel}; dW against fp64: {dw_rel64}")
+            folded = mods["scatter"]._folded(vq._normalised_codebook())
+            g_rows = g_out[:, n_prefix:].contiguous()
+            if g_rows.shape[-1] != folded[0].shape[1]:
+                g_rows = torch.nn.functional.pad(g_rows, (0, folded[0].shape[1] - g_rows.shape[-1]))
+            sides["table_grad"] = lambda: ops.embed_project_table_grad(g_rows, index, mods["scatter"].tokens, mods["scatter"].weights, folded[1], pad_mask=mask)
+            sides["table_grad"]()
+            inner = {s: inner_for(fn) for s, fn in sides.items()}
+            ms = {s: [] for s in sides}
+            for _ in range(args.reps):                          # the sides alternate
+                for s, fn in sides.items():
+                    ms[s].append(timed(fn, inner[s]))
+            with ops.ClockProbe(dev, max_seconds=10.0) as probe:
+                for _ in range(max(2, args.reps // 4)):
+                    timed(sides["scatter"], inner["scatter"])
+            clock = probe.result()
+            st = {s: stats(v) for s, v in ms.items()}
+            rows, hp = mods["scatter"].fold_table_shape()
+            entry = {"d": d, "n_e": n_e, "k": k, "H": h, "num_codes": num_codes, "positions": n_pos,
+                     "live_positions": int((~mask & (index < num_codes)).sum()), "table_rows": rows,
+                     "dense_weight_grad_flops": 2 * n_pos * 4 * d * h, "scatter_weight_grad_flops": 2 * rows * d * h,
+                     "activation_bytes": n_pos * 4 * d * 4, "table_grad_workspace_bytes": ops._lib.load().medtok_embed_table_grad_workspace_bytes(n_pos, 4, k, rows, hp),
+                     "out_rel_scatter_vs_dense": out_rel, "outputs_bit_equal": bool(torch.equal(outs["scatter"], outs["dense"])),
+                     "grad_rel_scatter_vs_dense": grad_rel, "dW_rel_vs_fp64": dw_rel64, "fold_builds": {s: mods[s].fold_builds for s in mods},
+                     "table_grad_ms": st["table_grad"]["ms_median"], "sort_share_of_table_grad": None,
+                     "clock_ghz": clock.get("ghz_mean"), "clock_region": "further scatter samples right behind the timed region"}
+            for s in (s for s in sides if s != "table_grad"):
+                entry[s] = dict(st[s], calls_per_sample=inner[s], spread=(st[s]["ms_max"] - st[s]["ms_min"]) / st[s]["ms_median"],
+                                peak_bytes=peak[s], positions_per_s=n_pos / (st[s]["ms_median"] * 1e-3))
+            entry["scatter_speedup_over_dense"] = st["dense"]["ms_median"] / st["scatter"]["ms_median"]
+            entry["scatter_not_slower_within_dense_spread"] = st["scatter"]["ms_median"] <= st["dense"]["ms_median"] + (st["dense"]["ms_max"] - st["dense"]["ms_min"])
+            entry["scatter_peak_smaller_than_dense"] = peak["scatter"] < peak["dense"]
+            if train:
+                entry["scatter_refold_not_slower_within_dense_spread"] = (st["scatter_refold"]["ms_median"] <= st["dense"]["ms_median"]
+                                                                          + (st["dense"]["ms_max"] - st["dense"]["ms_min"]))
+            result["cases"][f"{name}/{variant}" if train else name] = entry
+            for t in params + leaves:
+                t.grad = None
+            del outs, grads, index, mask, sides, g_rows, folded
+            torch.cuda.empty_cache()
+        del mods, plain, g_out, leaves, params
+        torch.cuda.empty_cache()
+    if args.out:
+        path = Path(args.out)
+        whole = json.loads(path.read_text()) if path.exists() else {}
+        whole.setdefault("table_grad", {})[form] = result
         path.parent.mkdir(parents=True, exist_ok=True)
         path.write_text(json.dumps(whole, indent=1) + "\n")
     print(json.dumps(result))
