@@ -10,7 +10,7 @@ VectorQuantizer) and the tokenizer call it, and that module re-exports every nam
   - _SoftVQFunction / _SoftVQMultiFunction / _DecodeFunction: a search, all searches of a forward, and decode under autograd
     (sparse backward; the code gradients summed per code without atomics);
   - _EmbedCodesFunction: the embedding lookup over the stored token table (MedTokEmbedding) and the gradient of its miss row;
-  - _EmbedProjectFunction: that lookup with the consumer's projector folded into the tables (forward on embed_project_kernel; dW, db
+  - _EmbedProjectFunction: that lookup with the consumer's projector folded into the tables (forward on embed_folded_kernel; dW, db
     and the miss row's gradient in a fixed order); _SmallLinearFunction / small_linear: y = x W^T + b on the exact fp32 product.
 """
 from __future__ import annotations
@@ -652,34 +652,43 @@ EMBED_PROJECT_GRAD_CHUNK = 16384          # positions per recomputed block of em
 
 
 class _EmbedProjectFunction(torch.autograd.Function):
-    """projector(MedTokEmbedding lookup) with a frozen codebook under autograd.  Forward: embed_project_kernel over the folded tables
-    (`folded` = ops.fold_projector's result, built from detached tensors: constants of this node).  Backward, from g [n, Hp] (the
-    padding columns dropped), deterministic and without float atomics:
-      dW        blocks of EMBED_PROJECT_GRAD_CHUNK positions in order: emb = embed_codes(...) fp32 recomputed (the only temporary:
-                chunk x S * d floats), dW += g_block^T . emb by the exact fp32 product;
-      db        the column sum of g (padded positions are the bias row: they count);
-      d miss    (sum of g over the unpadded miss positions, embed_codes_miss_grad at width H) . W.
-    The scatter form of dW (G_s^T . what_s over the folded tables' rows) is _EmbedProjectScatterFunction."""
+    """projector(MedTokEmbedding lookup) under autograd.  Forward: embed_folded_kernel over the folded tables (`folded` =
+    ops.fold_projector's result, built from detached tensors: constants of this node), the same bits in either gradient form.
+    `weight`: the codebook weight (padded to the normalised codebook's width) where it trains, which only the scatter form can serve,
+    else None.  `scatter` (not a tensor) chooses the backward, both deterministic and without float atomics:
+      dense (MedTokEmbedding's default), from g [n, Hp] converted to fp32 (the padding columns dropped), _embed_project_grads:
+        dW        blocks of EMBED_PROJECT_GRAD_CHUNK positions in order: emb = embed_codes(...) fp32 recomputed (the only temporary:
+                  chunk x S * d floats), dW += g_block^T . emb by the exact fp32 product;
+        db        the column sum of g (padded positions are the bias row: they count);
+        d miss    (sum of g over the unpadded miss positions, embed_codes_miss_grad at width H) . W.
+      scatter (grad_form="scatter"), _embed_project_scatter_grads: dW as G_s^T . what_s over the folded tables' rows, and the codebook's
+        gradient; a 16-bit upstream gradient goes to the sums as it is."""
 
     @staticmethod
-    def forward(ctx, w, b, miss, index, pad_mask, tokens, weights, what, regions, e_dim, folded, out_dtype, status):
+    def forward(ctx, w, b, miss, weight, index, pad_mask, tokens, weights, what, regions, e_dim, folded, out_dtype, status, scatter):
         table, row_regions, bias, miss_row = folded
         out = ops.embed_project(index, tokens, weights, table, row_regions, bias, miss_row=miss_row, pad_mask=pad_mask, out_dtype=out_dtype,
                                 status=status)
-        ctx.save_for_backward(w, miss, index, pad_mask, tokens, weights, what)
-        ctx.cfg = (tuple(regions), int(e_dim), b is not None)
+        ctx.save_for_backward(w, miss, weight, index, pad_mask, tokens, weights, what)
+        ctx.cfg = (tuple(regions), tuple(row_regions), int(e_dim), b is not None, bool(scatter))
         return out
 
     @staticmethod
     def backward(ctx, g):
-        w, miss, index, pad_mask, tokens, weights, what = ctx.saved_tensors
-        regions, e, has_bias = ctx.cfg
-        return _embed_project_grads(g, w, miss, index, pad_mask, tokens, weights, what, regions, e, has_bias, ctx.needs_input_grad[:3]) + (None,) * 10
+        w, miss, weight, index, pad_mask, tokens, weights, what = ctx.saved_tensors
+        regions, row_regions, e, has_bias, scatter = ctx.cfg
+        needs = ctx.needs_input_grad
+        if scatter:
+            grads = _embed_project_scatter_grads(g, w, miss, index, pad_mask, tokens, weights, what, regions, row_regions, e, has_bias, needs[:4],
+                                                 weight)
+        else:
+            grads = _embed_project_grads(g, w, miss, index, pad_mask, tokens, weights, what, regions, e, has_bias, needs[:3]) + (None,)
+        return grads + (None,) * 11
 
 
 def _embed_project_grads(g, w, miss, index, pad_mask, tokens, weights, what, regions, e, has_bias, needs):
-    """(dW, db, d miss) of the folded lookup from the upstream gradient g [n, >= H] of its rows: the arithmetic _EmbedProjectFunction
-    documents, shared with _EmbedSequenceFunction (which feeds it g[:, P:])"""
+    """(dW, db, d miss) of the folded lookup in the DENSE form, from the upstream gradient g [n, >= H] of its rows: the arithmetic
+    _EmbedProjectFunction documents, shared with _EmbedSequenceFunction (which feeds it g[:, P:])"""
     h, s, d = w.shape[0], len(regions), what.shape[1]
     n = index.numel()
     g = g.reshape(n, g.shape[-1])[:, :h].float().contiguous()          # (not -1: n may be 0)
@@ -759,29 +768,6 @@ def _embed_project_scatter_grads(g, w, miss, index, pad_mask, tokens, weights, w
     return dw, db, dmiss, dweight
 
 
-class _EmbedProjectScatterFunction(torch.autograd.Function):
-    """_EmbedProjectFunction with the scatter form of the backward (MedTokEmbedding(grad_form="scatter")) and one more differentiable
-    input, the codebook weight (padded to the normalised codebook's width; None where the codebook is frozen).  Forward: the same
-    kernel over the same folded tables, hence the same bits; the tables are folded from detached tensors, and this node's backward
-    supplies the codebook's gradient (_embed_project_scatter_grads).  A 16-bit upstream gradient goes to the sums as it is."""
-
-    @staticmethod
-    def forward(ctx, w, b, miss, weight, index, pad_mask, tokens, weights, what, regions, e_dim, folded, out_dtype, status):
-        table, row_regions, bias, miss_row = folded
-        out = ops.embed_project(index, tokens, weights, table, row_regions, bias, miss_row=miss_row, pad_mask=pad_mask, out_dtype=out_dtype,
-                                status=status)
-        ctx.save_for_backward(w, miss, weight, index, pad_mask, tokens, weights, what)
-        ctx.cfg = (tuple(regions), tuple(row_regions), int(e_dim), b is not None)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        w, miss, weight, index, pad_mask, tokens, weights, what = ctx.saved_tensors
-        regions, row_regions, e, has_bias = ctx.cfg
-        return _embed_project_scatter_grads(g, w, miss, index, pad_mask, tokens, weights, what, regions, row_regions, e, has_bias,
-                                            ctx.needs_input_grad[:4], weight) + (None,) * 10
-
-
 def _sequence_part_grads(g, needs, n_rows, segment_id, n_segments, pad_mask, n_prefix):
     """(d position_rows, d segment_rows[0], d segment_rows[1], d prefix) from g fp32 [B, P + L, W]; needs: which of the four are wanted"""
     dpos = dseg = dprefix = None
@@ -795,71 +781,47 @@ def _sequence_part_grads(g, needs, n_rows, segment_id, n_segments, pad_mask, n_p
 
 
 class _EmbedSequenceFunction(torch.autograd.Function):
-    """MedTokEmbedding.sequence over the folded tables under autograd: one launch forward (ops.embed_sequence).  Backward from g
-    [B, P + L, Hp] (a 16-bit g is converted to fp32 first, which is exact; the padding columns are dropped), deterministic and without
-    float atomics:
+    """MedTokEmbedding.sequence over the folded tables under autograd: one launch forward (ops.embed_sequence).  `weight` and `scatter`
+    as in _EmbedProjectFunction.  Backward from g [B, P + L, Hp], deterministic and without float atomics:
       d prefix                g[:, :P]
       d position_rows         ops.embed_sequence_position_grad (b ascending)
       d segment_rows[0], [1]  ops.embed_sequence_segment_grad, the same tensor for both terms (chunks of 256 positions, then chunk order)
-      dW, db, d miss          _EmbedProjectFunction's arithmetic on a contiguous copy of g[:, P:] (padded positions are the bias row: they
-                              count in db, as there)."""
-
-    @staticmethod
-    def forward(ctx, w, b, miss, position_rows, seg0, seg1, prefix, index, pad_mask, segment_id, tokens, weights, what, regions, e_dim, folded,
-                out_dtype, status):
-        table, row_regions, bias, miss_row = folded
-        terms = tuple(t for t in (seg0, seg1) if t is not None)
-        out = ops.embed_sequence(index, tokens, weights, table, row_regions, bias, miss_row=miss_row, pad_mask=pad_mask,
-                                 position_rows=position_rows, segment_id=segment_id, segment_rows=terms or None, prefix=prefix, width=w.shape[0],
-                                 out_dtype=out_dtype, status=status)
-        ctx.save_for_backward(w, miss, index, pad_mask, segment_id, tokens, weights, what)
-        ctx.cfg = (tuple(regions), int(e_dim), b is not None, None if position_rows is None else position_rows.shape[0],
-                   0 if seg0 is None else seg0.shape[1], 0 if prefix is None else prefix.shape[1])
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        w, miss, index, pad_mask, segment_id, tokens, weights, what = ctx.saved_tensors
-        regions, e, has_bias, n_rows, n_segments, n_prefix = ctx.cfg
-        g = g[:, :, :w.shape[0]].float().contiguous()
-        needs = ctx.needs_input_grad
-        grads = (None, None, None)
-        if any(needs[:3]):
-            grads = _embed_project_grads(g[:, n_prefix:].contiguous(), w, miss, index, pad_mask, tokens, weights, what, regions, e, has_bias,
-                                         needs[:3])
-        return grads + _sequence_part_grads(g, needs[3:7], n_rows, segment_id, n_segments, pad_mask, n_prefix) + (None,) * 11
-
-
-class _EmbedSequenceScatterFunction(torch.autograd.Function):
-    """_EmbedSequenceFunction with the scatter form of dW, db, d miss and the codebook's gradient (_embed_project_scatter_grads on a
-    contiguous copy of g[:, P:] in g's own dtype); the additive parts' gradients are _EmbedSequenceFunction's, from the fp32 g."""
+                              -- these three from g converted to fp32 (exact), the padding columns dropped;
+      dW, db, d miss          dense: _embed_project_grads on a contiguous copy of that fp32 g[:, P:] (padded positions are the bias row:
+                              they count in db, as there); scatter: with the codebook's gradient, _embed_project_scatter_grads on a
+                              contiguous copy of g[:, P:] in g's own dtype."""
 
     @staticmethod
     def forward(ctx, w, b, miss, weight, position_rows, seg0, seg1, prefix, index, pad_mask, segment_id, tokens, weights, what, regions, e_dim,
-                folded, out_dtype, status):
+                folded, out_dtype, status, scatter):
         table, row_regions, bias, miss_row = folded
         terms = tuple(t for t in (seg0, seg1) if t is not None)
         out = ops.embed_sequence(index, tokens, weights, table, row_regions, bias, miss_row=miss_row, pad_mask=pad_mask,
                                  position_rows=position_rows, segment_id=segment_id, segment_rows=terms or None, prefix=prefix, width=w.shape[0],
                                  out_dtype=out_dtype, status=status)
         ctx.save_for_backward(w, miss, weight, index, pad_mask, segment_id, tokens, weights, what)
-        ctx.cfg = (tuple(regions), tuple(row_regions), int(e_dim), b is not None, None if position_rows is None else position_rows.shape[0],
-                   0 if seg0 is None else seg0.shape[1], 0 if prefix is None else prefix.shape[1])
+        ctx.cfg = (tuple(regions), tuple(row_regions), int(e_dim), b is not None, bool(scatter),
+                   None if position_rows is None else position_rows.shape[0], 0 if seg0 is None else seg0.shape[1],
+                   0 if prefix is None else prefix.shape[1])
         return out
 
     @staticmethod
     def backward(ctx, g):
         w, miss, weight, index, pad_mask, segment_id, tokens, weights, what = ctx.saved_tensors
-        regions, row_regions, e, has_bias, n_rows, n_segments, n_prefix = ctx.cfg
+        regions, row_regions, e, has_bias, scatter, n_rows, n_segments, n_prefix = ctx.cfg
         needs = ctx.needs_input_grad
+        gf = g[:, :, :w.shape[0]].float().contiguous() if not scatter or any(needs[4:8]) else None
         grads = (None, None, None, None)
-        if any(needs[:4]):
+        if scatter and any(needs[:4]):
             grads = _embed_project_scatter_grads(g[:, n_prefix:].contiguous(), w, miss, index, pad_mask, tokens, weights, what, regions,
                                                  row_regions, e, has_bias, needs[:4], weight)
+        elif not scatter and any(needs[:3]):
+            grads = _embed_project_grads(gf[:, n_prefix:].contiguous(), w, miss, index, pad_mask, tokens, weights, what, regions, e, has_bias,
+                                         needs[:3]) + (None,)
         parts = (None, None, None, None)
         if any(needs[4:8]):
-            parts = _sequence_part_grads(g[:, :, :w.shape[0]].float().contiguous(), needs[4:8], n_rows, segment_id, n_segments, pad_mask, n_prefix)
-        return grads + parts + (None,) * 11
+            parts = _sequence_part_grads(gf, needs[4:8], n_rows, segment_id, n_segments, pad_mask, n_prefix)
+        return grads + parts + (None,) * 12
 
 
 class _EmbedSequenceRowsFunction(torch.autograd.Function):

@@ -17,7 +17,7 @@
 //   scan_kernel, radix_*_kernel    (ema_kernels.h) offsets[r] and the stable sort by key: row r's contributions are
 //                                  sorted[offsets[r] .. offsets[r + 1]) in increasing ct; the dead ones lie behind offsets[K].
 //   embed_code_grad_plan_kernel    chunks[r] = number of chunks of a row with MORE than one chunk, else 0 (scanned into first_chunk[]).
-//   embed_code_grad_chunk_kernel   the sums.  A row's list is cut into chunks of MEDTOK_EMBED_CODE_GRAD_CHUNK consecutive entries; a chunk
+//   embed_grad_chunk_kernel        the sums.  A row's list is cut into chunks of MEDTOK_EMBED_CODE_GRAD_CHUNK consecutive entries; a chunk
 //                                  is, per element, ONE fp32 chain acc = +0; acc = fmaf(w, g, acc) in list order.  Items [0, K) are the
 //                                  rows: a row of at most one chunk is finished here (an empty one: zeros), and every row's bin is
 //                                  written.  Items [K, K + Q) are the chunks of the longer rows (Q = ceil(2 * n * S * k / CHUNK) bounds
@@ -26,6 +26,15 @@
 //                                  whatever the code frequencies: a hot code's rows are spread over n / CHUNK wavefronts each.
 //   embed_code_grad_combine_kernel g_what[r] = the chunk sums of a row with several, added in chunk order from +0.
 // No float atomics anywhere; the order is fixed by the data alone (not by the device or a launch heuristic): two runs give the same bits.
+//
+// The FOLDED lookup (embed_folded_kernel) writes out[p, :] = bias + sum_s sum_j weights[c, s, j] * table[offset_s + tokens[c, s, j], :]:
+// every slot adds into the SAME hp columns.  Its per-table-row sums G[r] -- what the projector's weight gradient and the codebook's
+// gradient through the folded tables are both made of -- are the same pipeline over the table's rows with two differences, both template
+// arguments of the chunk kernel: a contribution carries the WHOLE row g[p, 0 : hp] (SLOT_BLOCKS = false: no slot offset in the gather
+// address; true: the slot's block g_out[p, s * d : (s + 1) * d] of embed_codes_kernel's rows), and g is read in its own type G_T =
+// float, _Float16 or __bf16: a 16-bit row is loaded as 16-bit (8 bytes per lane and load for four columns) and widened in registers,
+// which is exact; no fp32 copy of the [n, hp] gradient is made.  Keys, sort, plan, combine and the order are shared, so on g tiled S
+// times ([n, S * hp], block s a copy of g) the codebook gradient gives the same bits.
 //
 // The chunk kernel: LANES = 64 lanes per item (16 for d <= 64, four items per wavefront, as the other embed kernels).  Lane l of a group
 // loads the metadata of entry l of a round of LANES entries -- sorted ct, then index[p], then the weight: three dependent loads, all
@@ -86,13 +95,13 @@ __global__ __launch_bounds__(256) void embed_code_grad_plan_kernel(int *__restri
     counts[r] = len > MEDTOK_EMBED_CODE_GRAD_CHUNK ? (len + MEDTOK_EMBED_CODE_GRAD_CHUNK - 1) / MEDTOK_EMBED_CODE_GRAD_CHUNK : 0;
 }
 
-template <int LANES>
-__global__ __launch_bounds__(256) void embed_code_grad_chunk_kernel(const float *__restrict__ g_out, long g_stride, const int64_t *__restrict__ index,
-                                                                    const float *__restrict__ weights, long num_codes, int slots, int topk, int d,
-                                                                    const uint32_t *__restrict__ sorted, const int *__restrict__ offsets,
-                                                                    const int *__restrict__ first_chunk, long k_codes, long extra,
-                                                                    float *__restrict__ bins, float *__restrict__ g_what,
-                                                                    float *__restrict__ chunk_sums)
+template <int LANES, typename G_T, bool SLOT_BLOCKS>
+__global__ __launch_bounds__(256) void embed_grad_chunk_kernel(const G_T *__restrict__ g_out, long g_stride, const int64_t *__restrict__ index,
+                                                               const float *__restrict__ weights, long num_codes, int slots, int topk, int d,
+                                                               const uint32_t *__restrict__ sorted, const int *__restrict__ offsets,
+                                                               const int *__restrict__ first_chunk, long k_codes, long extra,
+                                                               float *__restrict__ bins, float *__restrict__ g_what,
+                                                               float *__restrict__ chunk_sums)
 {
     constexpr int CHUNK = MEDTOK_EMBED_CODE_GRAD_CHUNK;
     constexpr int R = LANES == 64 ? CHUNK / 64 : 4;               // rounds of LANES entries whose metadata a lane holds at once
@@ -137,11 +146,11 @@ __global__ __launch_bounds__(256) void embed_code_grad_chunk_kernel(const float 
             if (e < cnt) {
                 const long ct = sorted[first + e];
                 const long pos = ct / entries_per_pos;
-                const int rest = (int)(ct - pos * entries_per_pos), slot = rest / topk;
+                const int rest = (int)(ct - pos * entries_per_pos), slot = SLOT_BLOCKS ? rest / topk : 0;
                 const long c = index[pos];
                 if (c >= 0 && c < num_codes) {                    // (it was when the key was made: no address from an unchecked index)
                     wm[r] = weights[c * entries_per_pos + rest];  // 64-bit product
-                    gm[r] = pos * g_stride + (long)slot * d;
+                    gm[r] = pos * g_stride + (long)slot * d;      // the slot's block of the row; slot 0 without SLOT_BLOCKS: the whole row
                 }
             }
         }

@@ -21,22 +21,6 @@
 
 #define MEDTOK_EMBED_BAD_INDEX_BIT 4
 
-__device__ __forceinline__ void embed_store4(float *p, float4 v) { st4(p, v); }
-__device__ __forceinline__ void embed_store4(_Float16 *p, float4 v)
-{
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    h4 h;
-    h[0] = (_Float16)v.x; h[1] = (_Float16)v.y; h[2] = (_Float16)v.z; h[3] = (_Float16)v.w;
-    *reinterpret_cast<h4 *>(p) = h;
-}
-__device__ __forceinline__ void embed_store4(__bf16 *p, float4 v)
-{
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-    b4 h;
-    h[0] = (__bf16)v.x; h[1] = (__bf16)v.y; h[2] = (__bf16)v.z; h[3] = (__bf16)v.w;
-    *reinterpret_cast<b4 *>(p) = h;
-}
-
 template <int LANES, int MAXK, typename OUT>
 __global__ __launch_bounds__(256) void embed_codes_kernel(const int64_t *__restrict__ index, const uint8_t *__restrict__ pad, long items,
                                                           const int64_t *__restrict__ tokens, const float *__restrict__ weights, long num_codes,
@@ -101,7 +85,7 @@ __global__ __launch_bounds__(256) void embed_codes_kernel(const int64_t *__restr
         } else if (is_miss) {
             a = ld4(mrow + i);
         }
-        embed_store4(dst + i, a);
+        st4(dst + i, a);
     }
 }
 
@@ -155,35 +139,90 @@ __global__ __launch_bounds__(256) void embed_miss_grad_sum_kernel(const float *_
 // rows, so the projector is applied to the codebook once per weight version (ops.fold_projector: P_s = what[region_s] . W_s^T, one
 // [K_s, hp] table per slot, stacked in one buffer `table` with the slots' row offsets in reg.lo) and a position is
 //   out[p, h] = bias[h] + sum_s sum_j weights[c, s, j] * P_s[tokens[c, s, j], h]
-// One item = one position; all slots land in one output row.  LANES = 16, 32 or 64 lanes own it: lane i < slots * topk <= LANES loads
-// entry i of the code's ids and weights once (they are consecutive in memory), a shuffle hands them round, and the lanes cover the hp
-// columns as float4 (hp % 4 == 0; the host pads).  Per column ONE fp32 chain in a fixed order: acc = bias[h], then slots ascending,
-// then list order, acc = fmaf(w, P_s[id][h], acc); the k gathers of a slot are issued before its first fmaf.  Per position p with
+// One item = one output row; all slots land in it.  LANES = 16, 32 or 64 lanes own it: lane i < slots * topk <= LANES loads entry i of
+// the code's ids and weights once (they are consecutive in memory), a shuffle hands them round, and the lanes cover the hp columns as
+// float4 (hp % 4 == 0; the host pads).  Per column ONE fp32 chain in a fixed order: acc = bias[h], then slots ascending, then list
+// order, acc = fmaf(w, P_s[id][h], acc); the k gathers of a slot are issued before its first fmaf.  Per position p with
 // c = index[p] -- what projector(embed_codes(...)) gives:
 //   pad[p] != 0               the bias row; index[p] is not read, nor are the tables, and status is not touched
 //   0 <= c < num_codes        the chain above (a slot with an id outside its region contributes nothing, bit `slot` of *status)
 //   c == num_codes, miss_row  a copy of miss_row [hp] (W . miss + b, made with the tables)
 //   anything else             the bias row, bit 4 of *status
 // No index and no id forms an address before it has been checked; every product with c is 64-bit.  The shuffles run with every lane
-// of the wavefront active (the column loop's trip count is uniform; only loads, fmafs and stores are predicated).
-template <int LANES, int MAXK, typename OUT>
-__global__ __launch_bounds__(256) void embed_project_kernel(const int64_t *__restrict__ index, const uint8_t *__restrict__ pad, long n,
-                                                            const int64_t *__restrict__ tokens, const float *__restrict__ weights, long num_codes,
-                                                            int slots, int topk, const float *__restrict__ table, int hp, DecodeRegions reg,
-                                                            const float *__restrict__ bias, const float *__restrict__ miss_row,
-                                                            OUT *__restrict__ out, long out_stride, int *status)
+// of the wavefront active (the column loop's trip count is uniform; only loads, fmafs and stores are predicated).  OUT = float, _Float16 or __bf16: the finished fp32 value is rounded once, to nearest even.
+//
+// PARTS: the consumer's input sequence behind the lookup, in the same launch.  What the EHR model does between
+// `projector(med_code_emb[index])` and its first transformer layer (MedTok_EHR_Tutorial/EHRModel_token.py:220-232,
+// PositionalEncoding.forward :65-78): x + pe[:L], + two time embeddings gathered per code through the code's visit, torch.concat of
+// (cls, gender, ethnicity) rows in front.  Each of those steps reads and writes a [B, L, H] tensor; here the row is finished in
+// registers and stored once.  out is [B, P + L, width], one item per row (b, r):
+//   r < P                      a copy of prefix[b, r, :]
+//   p = r - P, pad[b, p] != 0  the lookup's row r0 (the bias row); nothing is added, and neither index[b, p] nor segment_id[b, p] is read
+//   otherwise                  ((r0 + position_rows[p]) + segment_rows0[b, g]) + segment_rows1[b, g],   g = segment_id[b, p]
+// plain fp32 additions in that order on the fp32 value of the lookup's chain (the library is built with -ffp-contract=off: the bits are
+// those of torch adding the tensors one after the other to the fp32 rows).  A miss position and a bad code index take the adds like
+// any unpadded position.  g outside [0, V): no segment term, bit MEDTOK_EMBED_BAD_SEGMENT_BIT of *status; no address is formed from
+// an unchecked id, and every address product is 64-bit.  Each absent part (position_rows, segment_id with its rows, the second segment
+// term, prefix) is a null pointer.  A prefix row runs through the same code as a padded position whose first row is prefix[b, r] (so
+// the shuffles see every lane under a uniform trip count).  The position row, the segment rows and the segment id are loaded before
+// the chain's first gather: they are in flight with the gathers.  PARTS is a compile-time switch because the epilogue costs registers
+// (20 VGPRs and a step of occupancy at <16, 8>): without it, nothing of it exists in the instantiation, and `len` (the positions per
+// batch row) and `parts` are not looked at (one argument list serves both).
+//
+// (MEDTOK_EMBED_BAD_SEGMENT_BIT, MEDTOK_EMBED_SEQ_MAX_TERMS, MEDTOK_EMBED_SEQ_GRAD_CHUNK and MEDTOK_EMBED_SEQ_MAX_SEGMENTS come from
+// include/medtok_vq.h: no second definition that could drift)
+struct EmbedSeqParts {
+    const float *position_rows;      // [>= len, width] or null
+    const int64_t *segment_id;       // [batch, len] or null
+    const float *segment_rows0;      // [batch, n_segments, width] or null
+    const float *segment_rows1;      // [batch, n_segments, width] or null (only with segment_rows0)
+    const float *prefix;             // [batch, n_prefix, width] or null
+    long n_segments;
+    long n_prefix;
+};
+
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+template <int LANES, int MAXK, typename OUT, bool PARTS>
+__global__ __launch_bounds__(256) void embed_folded_kernel(const int64_t *__restrict__ index, const uint8_t *__restrict__ pad, long items, long len,
+                                                           const int64_t *__restrict__ tokens, const float *__restrict__ weights, long num_codes,
+                                                           int slots, int topk, const float *__restrict__ table, int hp, DecodeRegions reg,
+                                                           const float *__restrict__ bias, const float *__restrict__ miss_row, EmbedSeqParts parts,
+                                                           OUT *__restrict__ out, long out_stride, int *status)
 {
     static_assert(LANES == 16 || LANES == 32 || LANES == 64, "a group is a power-of-two part of a wavefront");
     const int lane = threadIdx.x & 63, sub = threadIdx.x & (LANES - 1), base = lane & ~(LANES - 1);
-    long pos = (long)blockIdx.x * (256 / LANES) + threadIdx.x / LANES;
-    const bool live = pos < n;
-    if (!live) pos = 0;
-    // what this position is: the lanes of a group agree (one address each)
-    const bool padded = !live || (pad && pad[pos] != 0);
+    long item = (long)blockIdx.x * (256 / LANES) + threadIdx.x / LANES;
+    const bool live = item < items;
+    if (!live) item = 0;
+    long pos = item;                                              // the flat position whose index is looked up
+    [[maybe_unused]] long b = 0, r = 0, p = 0;                    // PARTS: batch row, row inside it, position inside it
+    [[maybe_unused]] bool is_prefix = false;
+    if constexpr (PARTS) {
+        const long per = parts.n_prefix + len;                    // rows per batch row (>= 1: items > 0)
+        b = item / per;
+        r = item - b * per;
+        is_prefix = r < parts.n_prefix;
+        p = is_prefix ? 0 : r - parts.n_prefix;                   // the position inside the batch row
+        pos = b * len + p;                                        // (only used where !is_prefix)
+    }
+    // what this row is: the lanes of a group agree (one address each)
+    const bool padded = !live || is_prefix || (pad && pad[pos] != 0);
     const long c = padded ? 0 : index[pos];
+    [[maybe_unused]] long g = 0;
+    if constexpr (PARTS) g = (padded || !parts.segment_id) ? 0 : parts.segment_id[pos];
     const bool is_code = !padded && c >= 0 && c < num_codes;
     const bool is_miss = !padded && miss_row && c == num_codes;
-    if (!padded && !is_code && !is_miss && sub == 0 && status) atomicOr(status, 1 << MEDTOK_EMBED_BAD_INDEX_BIT);
+    [[maybe_unused]] bool seg_on = false;
+    if constexpr (PARTS) {
+        seg_on = !padded && parts.segment_id && g >= 0 && g < parts.n_segments;
+        if (sub == 0 && status && !padded) {
+            if (!is_code && !is_miss) atomicOr(status, 1 << MEDTOK_EMBED_BAD_INDEX_BIT);
+            if (parts.segment_id && !seg_on) atomicOr(status, 1 << MEDTOK_EMBED_BAD_SEGMENT_BIT);
+        }
+    } else {
+        if (!padded && !is_code && !is_miss && sub == 0 && status) atomicOr(status, 1 << MEDTOK_EMBED_BAD_INDEX_BIT);
+    }
     const int entries = slots * topk;                             // <= LANES (checked on the host)
     const int eslot = sub / topk;                                 // the slot of this lane's entry
     long lo = reg.lo[0], size = reg.size[0];
@@ -207,11 +246,25 @@ __global__ __launch_bounds__(256) void embed_project_kernel(const int64_t *__res
         if (s < slots && ((mine >> (s * topk)) & ((1ull << topk) - 1ull)) != 0ull) bad_slots |= 1 << s;
     if (bad_slots && sub == 0 && status) atomicOr(status, bad_slots);      // (bad implies is_code: only such groups loaded an id)
     const float *first = is_miss ? miss_row : bias;
-    OUT *dst = out + pos * out_stride;
+    [[maybe_unused]] const float *prow = nullptr, *s0 = nullptr, *s1 = nullptr;
+    if constexpr (PARTS) {
+        first = is_prefix ? parts.prefix + (b * parts.n_prefix + r) * hp : first;
+        prow = (!padded && parts.position_rows) ? parts.position_rows + p * hp : nullptr;
+        const long srow = (b * parts.n_segments + (seg_on ? g : 0)) * hp;     // 64-bit; g was checked above
+        s0 = (seg_on && parts.segment_rows0) ? parts.segment_rows0 + srow : nullptr;
+        s1 = (seg_on && parts.segment_rows1) ? parts.segment_rows1 + srow : nullptr;
+    }
+    OUT *dst = out + item * out_stride;
     for (int i0 = 0; i0 < hp; i0 += LANES * 4) {                  // uniform over the wavefront: the shuffles below see every lane
         const int i = i0 + sub * 4;
         const bool on = live && i < hp;
         float4 a = on ? ld4(first + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        [[maybe_unused]] float4 pe = make_float4(0.f, 0.f, 0.f, 0.f), t0 = pe, t1 = pe;
+        if constexpr (PARTS) {
+            if (on && prow) pe = ld4(prow + i);                   // issued before the gathers: in flight with them
+            if (on && s0) t0 = ld4(s0 + i);
+            if (on && s1) t1 = ld4(s1 + i);
+        }
 #pragma unroll
         for (int s = 0; s < MEDTOK_DECODE_MAX_SLOTS; ++s) {
             if (s >= slots) break;
@@ -236,7 +289,12 @@ __global__ __launch_bounds__(256) void embed_project_kernel(const int64_t *__res
                     }
             }
         }
-        if (on) embed_store4(dst + i, a);
+        if constexpr (PARTS) {
+            if (prow) a = add4(a, pe);                            // (an absent part adds nothing at all: x + 0 would turn -0 into +0)
+            if (s0) a = add4(a, t0);
+            if (s1) a = add4(a, t1);
+        }
+        if (on) st4(dst + i, a);
     }
 }
 
@@ -251,7 +309,7 @@ __global__ __launch_bounds__(256) void embed_project_kernel(const int64_t *__res
 // compile-time constant, so the bits of the result never depend on the device or on a launch heuristic.  Position j of the chunk belongs
 // to wavefront j % 4, and a wavefront takes its positions one at a time, all slots:
 //   * up front, for each of its CHUNK / 4 positions: the mask byte and the index (not read under the mask), then the code's
-//     slots * topk <= 64 ids and weights, entry i in lane i as in embed_project_kernel -- every load of a level is in flight before the
+//     slots * topk <= 64 ids and weights, entry i in lane i as in embed_folded_kernel -- every load of a level is in flight before the
 //     first is used; ids are validated there (ballot), so no index and no id forms an address before it has been checked, and every
 //     product with a code index is 64-bit;
 //   * per position: lane l owns the float4 columns (r * 64 + l) * 4, r < R (R = 1, 4, 12 or 16 covers widths up to 256, 1024, 3072, 4096); a

@@ -9,9 +9,9 @@
 //   filter_f16.h          fp16-MFMA shortlist filter (three kernels), operand images, exact re-score
 //   assign_kernels.h      soft assignment, fixed-order fp64 sum
 //   decode_kernels.h      (token ids, weights) -> embedding, and its backward
-//   embed_kernels.h       code indices -> stored tokens -> embedding
-//   embed_sequence_kernels.h  the lookup's rows + position rows + segment rows behind prefix rows, and the additive rows' gradients
-//   embed_grad_kernels.h  the codebook's gradient through the lookup: sort keys, chunked per-row sums
+//   embed_kernels.h       code indices -> stored tokens -> embedding; the folded lookup, also as the consumer's input sequence; the pool
+//   embed_sequence_kernels.h  the input sequence over dense rows, and the additive rows' gradients
+//   embed_grad_kernels.h  the codebook's and the folded tables' gradient through the lookup: sort keys, chunked per-row sums
 //   train_kernels.h       sparse backward, normalize backward, InfoNCE
 //   loss_kernels.h        alignment / orthogonality losses
 //   attention_*.h         ragged cross-attention cores (fp32, fp16 x 3, LDS-DMA, two-tile, e_dim = 64) and their backward
@@ -193,6 +193,36 @@ __device__ __forceinline__ float wave_butterfly_sum(float p)
 
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+__device__ __forceinline__ void st1(float *p, float v) { *p = v; }
+
+// The same four columns in a 16-bit type.  A load widens in registers, which is exact; a store rounds each fp32 element once, to nearest even.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld4(const _Float16 *p)
+{
+    const f16x4 h = *reinterpret_cast<const f16x4 *>(p);
+    return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+}
+__device__ __forceinline__ float4 ld4(const __bf16 *p)
+{
+    const uint2 u = *reinterpret_cast<const uint2 *>(p);          // bf16 is the upper half of the fp32 with the same value
+    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                       __uint_as_float(u.y & 0xffff0000u));
+}
+__device__ __forceinline__ void st4(_Float16 *p, float4 v)
+{
+    f16x4 h;
+    h[0] = (_Float16)v.x; h[1] = (_Float16)v.y; h[2] = (_Float16)v.z; h[3] = (_Float16)v.w;
+    *reinterpret_cast<f16x4 *>(p) = h;
+}
+__device__ __forceinline__ void st4(__bf16 *p, float4 v)
+{
+    bf16x4 h;
+    h[0] = (__bf16)v.x; h[1] = (__bf16)v.y; h[2] = (__bf16)v.z; h[3] = (__bf16)v.w;
+    *reinterpret_cast<bf16x4 *>(p) = h;
+}
+__device__ __forceinline__ void st1(_Float16 *p, float v) { *p = (_Float16)v; }
+__device__ __forceinline__ void st1(__bf16 *p, float v) { *p = (__bf16)v; }
 
 // ================================================================= row norms and the exact fp32 search (kernels: search_f32.h)
 #include "search_f32.h"
@@ -1022,25 +1052,51 @@ static int decode_args(const char *fn, int64_t n, int slots, int topk, int64_t n
     return 0;
 }
 
+// a row stride of the caller's: 0 means dense; otherwise it covers the row and keeps float4 alignment
+static int row_stride(const char *fn, const char *name, int64_t &stride, int64_t least, const char *least_name)
+{
+    if (stride == 0) stride = least;
+    if (stride < least || (stride & 3)) return fail("%s: %s must be >= %s and a multiple of 4", fn, name, least_name);
+    return 0;
+}
+
+// (first template constant, list length) -> compile-time constants: fn(std::integral_constant<int, V>, std::integral_constant<int, MAXK>)
+// with V = the one of VALUES... that equals `value` (the lanes per group, or the pool's float4 per lane) and MAXK = 8 for lists of up to
+// 8 codes (they keep the 8-slot instantiation, as soft_assign), else MEDTOK_MAX_TOPK.  Every launch of a decode or lookup kernel that is
+// instantiated per list length goes through here, so only the listed instantiations exist.
+template <int... VALUES, typename F>
+static void dispatch_group(int value, int topk, F &&fn)
+{
+    auto by_k = [&](auto v) {
+        if (topk <= 8) fn(v, std::integral_constant<int, 8>{});
+        else fn(v, std::integral_constant<int, MEDTOK_MAX_TOPK>{});
+        return true;
+    };
+    (void)((value == VALUES && by_k(std::integral_constant<int, VALUES>{})) || ...);
+}
+
+// lanes per (row, slot) item of the decode-layout kernels: sixteen for rows of at most 64 floats, else a wavefront
+static inline int item_lanes(int d) { return d <= 64 ? 16 : 64; }
+
+// a launch holds at most 2^32 threads along x: 2^24 - 1 blocks of 256
+static const int64_t kMaxBlocks = 0xffffffffll / 256;
+
 extern "C" int medtok_decode_tokens_f32(const int64_t *tokens, const float *weights, int64_t n, int slots, int topk, const float *what,
                                         int64_t n_codes, int d, const int64_t *region_lo, const int64_t *region_size, float *out,
                                         int64_t out_stride, int *status, void *stream)
 {
     DecodeRegions reg;
     if (int rc = decode_args("decode_tokens", n, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
-    if (out_stride == 0) out_stride = (int64_t)slots * d;
-    if (out_stride < (int64_t)slots * d || (out_stride & 3)) return fail("decode_tokens: out_stride must be >= slots * d and a multiple of 4");
+    if (int rc = row_stride("decode_tokens", "out_stride", out_stride, (int64_t)slots * d, "slots * d")) return rc;
     if (n == 0) return 0;
     if (!tokens || !weights || !what || !out) return fail("decode_tokens: tokens, weights, what and out are required");
     const long items = (long)n * slots;
     hipStream_t s = (hipStream_t)stream;
-    // (rows of at most 64 floats: sixteen lanes per (row, slot); lists of up to 8 codes keep the 8-slot instantiation, as soft_assign)
-#define MEDTOK_DECODE_LAUNCH(LANES, MAXK)                                                                                              \
-    hipLaunchKernelGGL((decode_tokens_kernel<LANES, MAXK>), dim3((unsigned)((items + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s, \
-                       tokens, weights, items, slots, topk, what, d, reg, out, (long)out_stride, status)
-    if (d <= 64) { if (topk <= 8) MEDTOK_DECODE_LAUNCH(16, 8); else MEDTOK_DECODE_LAUNCH(16, MEDTOK_MAX_TOPK); }
-    else         { if (topk <= 8) MEDTOK_DECODE_LAUNCH(64, 8); else MEDTOK_DECODE_LAUNCH(64, MEDTOK_MAX_TOPK); }
-#undef MEDTOK_DECODE_LAUNCH
+    dispatch_group<16, 64>(item_lanes(d), topk, [&](auto lanes, auto maxk) {
+        constexpr int LANES = decltype(lanes)::value, MAXK = decltype(maxk)::value;
+        hipLaunchKernelGGL((decode_tokens_kernel<LANES, MAXK>), dim3((unsigned)((items + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s,
+                           tokens, weights, items, slots, topk, what, d, reg, out, (long)out_stride, status);
+    });
     return check_launch("decode_tokens");
 }
 
@@ -1051,47 +1107,69 @@ extern "C" int medtok_decode_tokens_backward_f32(const float *g_out, int64_t g_s
 {
     DecodeRegions reg;
     if (int rc = decode_args("decode_tokens_backward", n, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
-    if (g_stride == 0) g_stride = (int64_t)slots * d;
-    if (g_stride < (int64_t)slots * d || (g_stride & 3)) return fail("decode_tokens_backward: g_stride must be >= slots * d and a multiple of 4");
+    if (int rc = row_stride("decode_tokens_backward", "g_stride", g_stride, (int64_t)slots * d, "slots * d")) return rc;
     if (!g_w && !g_code) return fail("decode_tokens_backward: nothing to compute (g_w and g_code are both NULL)");
     if ((g_code != nullptr) != (g_ids != nullptr)) return fail("decode_tokens_backward: g_code and g_ids go together");
     if (n == 0) return 0;
     if (!g_out || !tokens || !weights || !what) return fail("decode_tokens_backward: g_out, tokens, weights and what are required");
     const long items = (long)n * slots;
     hipStream_t s = (hipStream_t)stream;
-#define MEDTOK_DECODE_LAUNCH(LANES, MAXK)                                                                                                       \
-    hipLaunchKernelGGL((decode_tokens_backward_kernel<LANES, MAXK>), dim3((unsigned)((items + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s, \
-                       g_out, (long)g_stride, tokens, weights, items, slots, topk, what, d, reg, g_w, g_code, g_ids, status)
-    if (d <= 64) { if (topk <= 8) MEDTOK_DECODE_LAUNCH(16, 8); else MEDTOK_DECODE_LAUNCH(16, MEDTOK_MAX_TOPK); }
-    else         { if (topk <= 8) MEDTOK_DECODE_LAUNCH(64, 8); else MEDTOK_DECODE_LAUNCH(64, MEDTOK_MAX_TOPK); }
-#undef MEDTOK_DECODE_LAUNCH
+    dispatch_group<16, 64>(item_lanes(d), topk, [&](auto lanes, auto maxk) {
+        constexpr int LANES = decltype(lanes)::value, MAXK = decltype(maxk)::value;
+        hipLaunchKernelGGL((decode_tokens_backward_kernel<LANES, MAXK>), dim3((unsigned)((items + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s,
+                           g_out, (long)g_stride, tokens, weights, items, slots, topk, what, d, reg, g_w, g_code, g_ids, status);
+    });
     return check_launch("decode_tokens_backward");
 }
 
 // ================================================================= embedding lookup: code indices -> stored tokens -> embedding
 #include "embed_kernels.h"
 
-// both output widths of medtok_embed_codes_*: decode's checks, then one launch
+// What every medtok_embed_* lookup entry is given: the positions' code indices and mask, the stored lists [num_codes, slots, topk], and
+// the table they point into -- the normalised codebook [rows, width = d] or the folded tables [rows, width = hp] -- with a region of its
+// rows per slot.  The extern "C" entries fill it and hand it on.
+struct EmbedLookup {
+    const int64_t *index;
+    const uint8_t *pad;
+    const int64_t *tokens;
+    const float *weights;
+    int64_t num_codes;
+    int slots, topk;
+    const float *table;
+    int64_t rows;
+    int width;
+    const int64_t *region_lo, *region_size;
+};
+
+// the shape checks of a lookup over n positions: decode's, the range of num_codes, and, for a kernel that gives a code's entries one lane
+// each (the folded lookup, the pool), that they fit a wavefront; fills the regions
+static int embed_args(const char *fn, const EmbedLookup &a, int64_t n, bool entry_per_lane, DecodeRegions &reg)
+{
+    if (int rc = decode_args(fn, n, a.slots, a.topk, a.rows, a.width, a.region_lo, a.region_size, reg)) return rc;
+    if (a.num_codes < 1 || a.num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)a.num_codes);
+    if (entry_per_lane && a.slots * a.topk > 64)
+        return fail("%s: slots * topk = %d entries per code exceed one wavefront", fn, a.slots * a.topk);
+    return 0;
+}
+
+// all output widths of medtok_embed_codes_*: the checks, then one launch
 template <typename OUT>
-static int embed_codes_launch(const char *fn, const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
-                              int64_t num_codes, int slots, int topk, const float *what, int64_t n_codes, int d, const int64_t *region_lo,
-                              const int64_t *region_size, const float *miss, OUT *out, int64_t out_stride, int *status, void *stream)
+static int embed_codes_launch(const char *fn, const EmbedLookup &a, int64_t n, const float *miss, OUT *out, int64_t out_stride, int *status,
+                              void *stream)
 {
     DecodeRegions reg;
-    if (int rc = decode_args(fn, n, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
-    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
-    if (out_stride == 0) out_stride = (int64_t)slots * d;
-    if (out_stride < (int64_t)slots * d || (out_stride & 3)) return fail("%s: out_stride must be >= slots * d and a multiple of 4", fn);
+    if (int rc = embed_args(fn, a, n, false, reg)) return rc;
+    if (int rc = row_stride(fn, "out_stride", out_stride, (int64_t)a.slots * a.width, "slots * d")) return rc;
     if (n == 0) return 0;
-    if (!index || !tokens || !weights || !what || !out) return fail("%s: index, tokens, weights, what and out are required", fn);
-    const long items = (long)n * slots;
+    if (!a.index || !a.tokens || !a.weights || !a.table || !out) return fail("%s: index, tokens, weights, what and out are required", fn);
+    const long items = (long)n * a.slots;
     hipStream_t s = (hipStream_t)stream;
-#define MEDTOK_EMBED_LAUNCH(LANES, MAXK)                                                                                                    \
-    hipLaunchKernelGGL((embed_codes_kernel<LANES, MAXK, OUT>), dim3((unsigned)((items + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s, \
-                       index, pad, items, tokens, weights, (long)num_codes, slots, topk, what, d, reg, miss, out, (long)out_stride, status)
-    if (d <= 64) { if (topk <= 8) MEDTOK_EMBED_LAUNCH(16, 8); else MEDTOK_EMBED_LAUNCH(16, MEDTOK_MAX_TOPK); }
-    else         { if (topk <= 8) MEDTOK_EMBED_LAUNCH(64, 8); else MEDTOK_EMBED_LAUNCH(64, MEDTOK_MAX_TOPK); }
-#undef MEDTOK_EMBED_LAUNCH
+    dispatch_group<16, 64>(item_lanes(a.width), a.topk, [&](auto lanes, auto maxk) {
+        constexpr int LANES = decltype(lanes)::value, MAXK = decltype(maxk)::value;
+        hipLaunchKernelGGL((embed_codes_kernel<LANES, MAXK, OUT>), dim3((unsigned)((items + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s,
+                           a.index, a.pad, items, a.tokens, a.weights, (long)a.num_codes, a.slots, a.topk, a.table, a.width, reg, miss, out,
+                           (long)out_stride, status);
+    });
     return check_launch(fn);
 }
 
@@ -1100,8 +1178,8 @@ extern "C" int medtok_embed_codes_f32(const int64_t *index, const uint8_t *pad, 
                                       const int64_t *region_lo, const int64_t *region_size, const float *miss, float *out, int64_t out_stride,
                                       int *status, void *stream)
 {
-    return embed_codes_launch<float>("embed_codes", index, pad, n, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo, region_size,
-                                     miss, out, out_stride, status, stream);
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo, region_size};
+    return embed_codes_launch<float>("embed_codes", a, n, miss, out, out_stride, status, stream);
 }
 
 extern "C" int medtok_embed_codes_f16(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
@@ -1109,40 +1187,38 @@ extern "C" int medtok_embed_codes_f16(const int64_t *index, const uint8_t *pad, 
                                       const int64_t *region_lo, const int64_t *region_size, const float *miss, void *out, int64_t out_stride,
                                       int bf16, int *status, void *stream)
 {
-    if (bf16)
-        return embed_codes_launch<__bf16>("embed_codes_f16(bf16)", index, pad, n, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo,
-                                          region_size, miss, (__bf16 *)out, out_stride, status, stream);
-    return embed_codes_launch<_Float16>("embed_codes_f16", index, pad, n, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo,
-                                        region_size, miss, (_Float16 *)out, out_stride, status, stream);
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo, region_size};
+    if (bf16) return embed_codes_launch<__bf16>("embed_codes_f16(bf16)", a, n, miss, (__bf16 *)out, out_stride, status, stream);
+    return embed_codes_launch<_Float16>("embed_codes_f16", a, n, miss, (_Float16 *)out, out_stride, status, stream);
 }
 
-// both output widths of medtok_embed_project_*: the lookup with the projector folded into per-slot tables (embed_project_kernel)
+// Every entry of the folded lookup (embed_folded_kernel): medtok_embed_project_* (parts == nullptr: one output row per position) and
+// medtok_embed_sequence_* (items = batch * (n_prefix + len) output rows over batch * len positions).
 template <typename OUT>
-static int embed_project_launch(const char *fn, const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
-                                int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp, const int64_t *row_lo,
-                                const int64_t *row_size, const float *bias, const float *miss_row, OUT *out, int64_t out_stride, int *status,
-                                void *stream)
+static int embed_folded_launch(const char *fn, const EmbedLookup &a, int64_t positions, int64_t items, int64_t len, const EmbedSeqParts *parts,
+                               const float *bias, const float *miss_row, OUT *out, int64_t out_stride, int *status, void *stream)
 {
     DecodeRegions reg;
-    if (int rc = decode_args(fn, n, slots, topk, n_rows, hp, row_lo, row_size, reg)) return rc;
-    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
-    if (slots * topk > 64) return fail("%s: slots * topk = %d entries per code exceed one wavefront", fn, slots * topk);
-    if (out_stride == 0) out_stride = hp;
-    if (out_stride < hp || (out_stride & 3)) return fail("%s: out_stride must be >= hp and a multiple of 4", fn);
-    if (n == 0) return 0;
-    if (!index || !tokens || !weights || !table || !bias || !out) return fail("%s: index, tokens, weights, table, bias and out are required", fn);
+    if (int rc = embed_args(fn, a, positions, true, reg)) return rc;
+    if (int rc = row_stride(fn, "out_stride", out_stride, a.width, "hp")) return rc;
+    if (items == 0) return 0;
+    if (!a.tokens || !a.weights || !a.table || !bias || !out || (positions > 0 && !a.index))
+        return fail("%s: index, tokens, weights, table, bias and out are required", fn);
     hipStream_t s = (hipStream_t)stream;
     // the smallest group that holds the code's slots * topk entries and, up to a wavefront, covers the row in one float4 pass
-    int lanes = 16;
-    while (lanes < 64 && (lanes < slots * topk || lanes * 4 < hp)) lanes *= 2;
-#define MEDTOK_PROJECT_LAUNCH(LANES, MAXK)                                                                                               \
-    hipLaunchKernelGGL((embed_project_kernel<LANES, MAXK, OUT>), dim3((unsigned)((n + 256 / LANES - 1) / (256 / LANES))), dim3(256), 0, s, \
-                       index, pad, (long)n, tokens, weights, (long)num_codes, slots, topk, table, hp, reg, bias, miss_row, out,          \
-                       (long)out_stride, status)
-#define MEDTOK_PROJECT_LANES(LANES) do { if (topk <= 8) MEDTOK_PROJECT_LAUNCH(LANES, 8); else MEDTOK_PROJECT_LAUNCH(LANES, MEDTOK_MAX_TOPK); } while (0)
-    if (lanes == 16) MEDTOK_PROJECT_LANES(16); else if (lanes == 32) MEDTOK_PROJECT_LANES(32); else MEDTOK_PROJECT_LANES(64);
-#undef MEDTOK_PROJECT_LANES
-#undef MEDTOK_PROJECT_LAUNCH
+    int group = 16;
+    while (group < 64 && (group < a.slots * a.topk || group * 4 < a.width)) group *= 2;
+    const int64_t blocks = (items + 256 / group - 1) / (256 / group);
+    if (parts && blocks > kMaxBlocks) return fail("%s: %ld rows exceed one launch (%ld blocks of 256 threads)", fn, (long)items, (long)kMaxBlocks);
+    dispatch_group<16, 32, 64>(group, a.topk, [&](auto lanes, auto maxk) {
+        auto launch = [&](auto with_parts) {
+            hipLaunchKernelGGL((embed_folded_kernel<decltype(lanes)::value, decltype(maxk)::value, OUT, decltype(with_parts)::value>),
+                               dim3((unsigned)blocks), dim3(256), 0, s, a.index, a.pad, (long)items, (long)len, a.tokens, a.weights,
+                               (long)a.num_codes, a.slots, a.topk, a.table, a.width, reg, bias, miss_row, parts ? *parts : EmbedSeqParts{}, out,
+                               (long)out_stride, status);
+        };
+        if (parts) launch(std::true_type{}); else launch(std::false_type{});
+    });
     return check_launch(fn);
 }
 
@@ -1151,8 +1227,8 @@ extern "C" int medtok_embed_project_f32(const int64_t *index, const uint8_t *pad
                                         const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row, float *out,
                                         int64_t out_stride, int *status, void *stream)
 {
-    return embed_project_launch<float>("embed_project", index, pad, n, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo, row_size,
-                                       bias, miss_row, out, out_stride, status, stream);
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo, row_size};
+    return embed_folded_launch<float>("embed_project", a, n, n, 0, nullptr, bias, miss_row, out, out_stride, status, stream);
 }
 
 extern "C" int medtok_embed_project_f16(const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, const float *weights,
@@ -1160,11 +1236,10 @@ extern "C" int medtok_embed_project_f16(const int64_t *index, const uint8_t *pad
                                         const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row, void *out,
                                         int64_t out_stride, int bf16, int *status, void *stream)
 {
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo, row_size};
     if (bf16)
-        return embed_project_launch<__bf16>("embed_project_f16(bf16)", index, pad, n, tokens, weights, num_codes, slots, topk, table, n_rows, hp,
-                                            row_lo, row_size, bias, miss_row, (__bf16 *)out, out_stride, status, stream);
-    return embed_project_launch<_Float16>("embed_project_f16", index, pad, n, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo,
-                                          row_size, bias, miss_row, (_Float16 *)out, out_stride, status, stream);
+        return embed_folded_launch<__bf16>("embed_project_f16(bf16)", a, n, n, 0, nullptr, bias, miss_row, (__bf16 *)out, out_stride, status, stream);
+    return embed_folded_launch<_Float16>("embed_project_f16", a, n, n, 0, nullptr, bias, miss_row, (_Float16 *)out, out_stride, status, stream);
 }
 
 extern "C" size_t medtok_embed_codes_miss_grad_workspace_bytes(int64_t n, int width)
@@ -1212,22 +1287,19 @@ extern "C" int medtok_embed_pool_f32(const int64_t *index, const uint8_t *pad, i
                                      int64_t out_stride, int *counts, int *status, void *ws, size_t ws_bytes, void *stream)
 {
     const char *fn = "embed_pool";
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo, region_size};
     DecodeRegions reg;
     if (bag_len < 0 || bag_len >= (1ll << 31)) return fail("%s: bag_len=%ld unsupported", fn, (long)bag_len);
-    if (int rc = decode_args(fn, bags, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
-    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
-    if (slots * topk > 64) return fail("%s: slots * topk = %d entries per code exceed one wavefront", fn, slots * topk);
+    if (int rc = embed_args(fn, a, bags, true, reg)) return rc;
     const int64_t wide = (int64_t)slots * d;
     if (wide > MEDTOK_EMBED_POOL_MAX_WIDTH) return fail("%s: rows of slots * d = %ld floats exceed %d", fn, (long)wide, MEDTOK_EMBED_POOL_MAX_WIDTH);
     const int width = (int)wide;
-    if (out_stride == 0) out_stride = width;
-    if (out_stride < width || (out_stride & 3)) return fail("%s: out_stride must be >= slots * d and a multiple of 4", fn);
+    if (int rc = row_stride(fn, "out_stride", out_stride, width, "slots * d")) return rc;
     if (bags == 0) return 0;
     const int64_t chunks = (bag_len + MEDTOK_EMBED_POOL_CHUNK - 1) / MEDTOK_EMBED_POOL_CHUNK;
-    // a launch holds at most 2^32 threads along x: 2^24 - 1 blocks of 256 (one per chunk in the first kernel, one per bag in the second)
-    const int64_t max_blocks = 0xffffffffll / 256;
-    if (bags > max_blocks || (chunks && bags > max_blocks / chunks))
-        return fail("%s: %ld bags x %ld chunks exceed one launch (%ld blocks of 256 threads)", fn, (long)bags, (long)chunks, (long)max_blocks);
+    // (one block per chunk in the first kernel, one per bag in the second)
+    if (bags > kMaxBlocks || (chunks && bags > kMaxBlocks / chunks))
+        return fail("%s: %ld bags x %ld chunks exceed one launch (%ld blocks of 256 threads)", fn, (long)bags, (long)chunks, (long)kMaxBlocks);
     if (!tokens || !weights || !what || !out || (bag_len > 0 && !index)) return fail("%s: index, tokens, weights, what and out are required", fn);
     const size_t need = medtok_embed_pool_workspace_bytes(bags, bag_len, width);
     if (need && (!ws || ws_bytes < need)) return fail("%s: workspace too small (%zu bytes given, %zu needed)", fn, ws_bytes, need);
@@ -1235,19 +1307,14 @@ extern "C" int medtok_embed_pool_f32(const int64_t *index, const uint8_t *pad, i
     float *partial = (float *)ws;
     int *chunk_counts = (int *)((char *)ws + pool_round(blocks * (size_t)width * sizeof(float)));
     hipStream_t s = (hipStream_t)stream;
-#define MEDTOK_POOL_LAUNCH(R, MAXK)                                                                                                        \
-    hipLaunchKernelGGL((embed_pool_partial_kernel<R, MAXK>), dim3((unsigned)blocks), dim3(256), (size_t)width * sizeof(float), s, index, pad, \
-                       (long)bag_len, (int)chunks, tokens, weights, (long)num_codes, slots, topk, what, d, reg, miss, normalize, partial,      \
-                       chunk_counts, status)
-#define MEDTOK_POOL_ROWS(R) do { if (topk <= 8) MEDTOK_POOL_LAUNCH(R, 8); else MEDTOK_POOL_LAUNCH(R, MEDTOK_MAX_TOPK); } while (0)
-    if (blocks) {                                                  // (floats per lane by the row's width: 4, 16, 48 or 64)
-        if (width <= 256) MEDTOK_POOL_ROWS(1);
-        else if (width <= 1024) MEDTOK_POOL_ROWS(4);
-        else if (width <= 3072) MEDTOK_POOL_ROWS(12);
-        else MEDTOK_POOL_ROWS(16);
-    }
-#undef MEDTOK_POOL_ROWS
-#undef MEDTOK_POOL_LAUNCH
+    // (float4 per lane by the row's width: 4, 16, 48 or 64 floats)
+    const int per_lane = width <= 256 ? 1 : width <= 1024 ? 4 : width <= 3072 ? 12 : 16;
+    if (blocks)
+        dispatch_group<1, 4, 12, 16>(per_lane, topk, [&](auto r, auto maxk) {
+            hipLaunchKernelGGL((embed_pool_partial_kernel<decltype(r)::value, decltype(maxk)::value>), dim3((unsigned)blocks), dim3(256),
+                               (size_t)width * sizeof(float), s, index, pad, (long)bag_len, (int)chunks, tokens, weights, (long)num_codes, slots,
+                               topk, what, d, reg, miss, normalize, partial, chunk_counts, status);
+        });
     hipLaunchKernelGGL(embed_pool_finish_kernel, dim3((unsigned)bags, (unsigned)((width + 1023) / 1024)), dim3(256), 0, s, (const float *)partial,
                        (const int *)chunk_counts, (int)chunks, width, out, (long)out_stride, counts);
     return check_launch(fn);
@@ -1277,9 +1344,6 @@ extern "C" int medtok_embed_pool_miss_grad_f32(const float *g_out, int64_t g_str
 // ---- the consumer's input sequence behind the lookup: position rows, segment rows and prefix rows in the lookup's launch
 #include "embed_sequence_kernels.h"
 
-// a launch holds at most 2^32 threads along x: 2^24 - 1 blocks of 256
-static const int64_t kSeqMaxBlocks = 0xffffffffll / 256;
-
 // the checks every medtok_embed_sequence_* entry shares: shapes and which parts are present, before any pointer of a tensor is looked at
 static int sequence_parts(const char *fn, int64_t batch, int64_t len, int width, const float *position_rows, int64_t n_position_rows,
                           const int64_t *segment_id, const float *segment_rows0, const float *segment_rows1, int64_t n_segments,
@@ -1306,43 +1370,18 @@ static int sequence_parts(const char *fn, int64_t batch, int64_t len, int width,
     return 0;
 }
 
-// both output widths of medtok_embed_sequence_*: embed_project's checks, the parts, then one launch
+// all output widths of medtok_embed_sequence_*: the parts, then the folded lookup's checks and launch
 template <typename OUT>
-static int embed_sequence_launch(const char *fn, const int64_t *index, const uint8_t *pad, int64_t batch, int64_t len, const int64_t *tokens,
-                                 const float *weights, int64_t num_codes, int slots, int topk, const float *table, int64_t n_rows, int hp,
-                                 const int64_t *row_lo, const int64_t *row_size, const float *bias, const float *miss_row,
+static int embed_sequence_launch(const char *fn, const EmbedLookup &a, int64_t batch, int64_t len, const float *bias, const float *miss_row,
                                  const float *position_rows, int64_t n_position_rows, const int64_t *segment_id, const float *segment_rows0,
                                  const float *segment_rows1, int64_t n_segments, const float *prefix, int64_t n_prefix, OUT *out,
                                  int64_t out_stride, int *status, void *stream)
 {
-    DecodeRegions reg;
     EmbedSeqParts parts;
-    if (int rc = sequence_parts(fn, batch, len, hp, position_rows, n_position_rows, segment_id, segment_rows0, segment_rows1, n_segments, prefix,
-                                n_prefix, parts))
+    if (int rc = sequence_parts(fn, batch, len, a.width, position_rows, n_position_rows, segment_id, segment_rows0, segment_rows1, n_segments,
+                                prefix, n_prefix, parts))
         return rc;
-    if (int rc = decode_args(fn, batch * len, slots, topk, n_rows, hp, row_lo, row_size, reg)) return rc;
-    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
-    if (slots * topk > 64) return fail("%s: slots * topk = %d entries per code exceed one wavefront", fn, slots * topk);
-    if (out_stride == 0) out_stride = hp;
-    if (out_stride < hp || (out_stride & 3)) return fail("%s: out_stride must be >= hp and a multiple of 4", fn);
-    const int64_t items = batch * (n_prefix + len);
-    if (items == 0) return 0;
-    if (!tokens || !weights || !table || !bias || !out || (len > 0 && !index))
-        return fail("%s: index, tokens, weights, table, bias and out are required", fn);
-    hipStream_t s = (hipStream_t)stream;
-    // the smallest group that holds the code's slots * topk entries and, up to a wavefront, covers the row in one float4 pass
-    int lanes = 16;
-    while (lanes < 64 && (lanes < slots * topk || lanes * 4 < hp)) lanes *= 2;
-    const int64_t blocks = (items + 256 / lanes - 1) / (256 / lanes);
-    if (blocks > kSeqMaxBlocks) return fail("%s: %ld rows exceed one launch (%ld blocks of 256 threads)", fn, (long)items, (long)kSeqMaxBlocks);
-#define MEDTOK_SEQUENCE_LAUNCH(LANES, MAXK)                                                                                              \
-    hipLaunchKernelGGL((embed_sequence_kernel<LANES, MAXK, OUT>), dim3((unsigned)blocks), dim3(256), 0, s, index, pad, (long)items, (long)len, \
-                       tokens, weights, (long)num_codes, slots, topk, table, hp, reg, bias, miss_row, parts, out, (long)out_stride, status)
-#define MEDTOK_SEQUENCE_LANES(LANES) do { if (topk <= 8) MEDTOK_SEQUENCE_LAUNCH(LANES, 8); else MEDTOK_SEQUENCE_LAUNCH(LANES, MEDTOK_MAX_TOPK); } while (0)
-    if (lanes == 16) MEDTOK_SEQUENCE_LANES(16); else if (lanes == 32) MEDTOK_SEQUENCE_LANES(32); else MEDTOK_SEQUENCE_LANES(64);
-#undef MEDTOK_SEQUENCE_LANES
-#undef MEDTOK_SEQUENCE_LAUNCH
-    return check_launch(fn);
+    return embed_folded_launch<OUT>(fn, a, batch * len, batch * (n_prefix + len), len, &parts, bias, miss_row, out, out_stride, status, stream);
 }
 
 extern "C" int medtok_embed_sequence_f32(const int64_t *index, const uint8_t *pad, int64_t batch, int64_t len, const int64_t *tokens,
@@ -1352,9 +1391,9 @@ extern "C" int medtok_embed_sequence_f32(const int64_t *index, const uint8_t *pa
                                          const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
                                          int64_t n_prefix, float *out, int64_t out_stride, int *status, void *stream)
 {
-    return embed_sequence_launch<float>("embed_sequence", index, pad, batch, len, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo,
-                                        row_size, bias, miss_row, position_rows, n_position_rows, segment_id, segment_rows0, segment_rows1,
-                                        n_segments, prefix, n_prefix, out, out_stride, status, stream);
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo, row_size};
+    return embed_sequence_launch<float>("embed_sequence", a, batch, len, bias, miss_row, position_rows, n_position_rows, segment_id, segment_rows0,
+                                        segment_rows1, n_segments, prefix, n_prefix, out, out_stride, status, stream);
 }
 
 extern "C" int medtok_embed_sequence_f16(const int64_t *index, const uint8_t *pad, int64_t batch, int64_t len, const int64_t *tokens,
@@ -1364,13 +1403,12 @@ extern "C" int medtok_embed_sequence_f16(const int64_t *index, const uint8_t *pa
                                          const float *segment_rows0, const float *segment_rows1, int64_t n_segments, const float *prefix,
                                          int64_t n_prefix, void *out, int64_t out_stride, int bf16, int *status, void *stream)
 {
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, table, n_rows, hp, row_lo, row_size};
     if (bf16)
-        return embed_sequence_launch<__bf16>("embed_sequence_f16(bf16)", index, pad, batch, len, tokens, weights, num_codes, slots, topk, table,
-                                             n_rows, hp, row_lo, row_size, bias, miss_row, position_rows, n_position_rows, segment_id,
+        return embed_sequence_launch<__bf16>("embed_sequence_f16(bf16)", a, batch, len, bias, miss_row, position_rows, n_position_rows, segment_id,
                                              segment_rows0, segment_rows1, n_segments, prefix, n_prefix, (__bf16 *)out, out_stride, status, stream);
-    return embed_sequence_launch<_Float16>("embed_sequence_f16", index, pad, batch, len, tokens, weights, num_codes, slots, topk, table, n_rows, hp,
-                                           row_lo, row_size, bias, miss_row, position_rows, n_position_rows, segment_id, segment_rows0,
-                                           segment_rows1, n_segments, prefix, n_prefix, (_Float16 *)out, out_stride, status, stream);
+    return embed_sequence_launch<_Float16>("embed_sequence_f16", a, batch, len, bias, miss_row, position_rows, n_position_rows, segment_id,
+                                           segment_rows0, segment_rows1, n_segments, prefix, n_prefix, (_Float16 *)out, out_stride, status, stream);
 }
 
 // both output widths of medtok_embed_sequence_rows_*: the epilogue over dense fp32 rows
@@ -1389,7 +1427,7 @@ static int embed_sequence_rows_launch(const char *fn, const float *rows, const u
     if (!out || (len > 0 && !rows)) return fail("%s: rows and out are required", fn);
     const int vec = (width & 3) ? 1 : 4;
     const int64_t blocks = (items * (width / vec) + 255) / 256;   // items < 2^31, width < 2^31: no overflow
-    if (blocks > kSeqMaxBlocks) return fail("%s: %ld rows of %d exceed one launch (%ld blocks of 256 threads)", fn, (long)items, width, (long)kSeqMaxBlocks);
+    if (blocks > kMaxBlocks) return fail("%s: %ld rows of %d exceed one launch (%ld blocks of 256 threads)", fn, (long)items, width, (long)kMaxBlocks);
     hipStream_t s = (hipStream_t)stream;
     if (vec == 4)
         hipLaunchKernelGGL((embed_sequence_rows_kernel<4, OUT>), dim3((unsigned)blocks), dim3(256), 0, s, rows, pad, (long)items, (long)len, width, parts,
@@ -1450,7 +1488,7 @@ extern "C" int medtok_embed_sequence_segment_grad_f32(const float *g, const uint
     while (tile > 4 && ((int64_t)n_segments * tile * 4 > 65536 || tile / 2 >= width)) tile /= 2;
     const int64_t col_blocks = (width + tile - 1) / tile;
     const int64_t total = batch * n_segments * (int64_t)width;
-    if (batch * chunks > kSeqMaxBlocks || col_blocks > 65535 || (total + 255) / 256 > kSeqMaxBlocks)
+    if (batch * chunks > kMaxBlocks || col_blocks > 65535 || (total + 255) / 256 > kMaxBlocks)
         return fail("%s: batch=%ld x len=%ld x n_segments=%ld x width=%d exceed one launch", fn, (long)batch, (long)len, (long)n_segments, width);
     if (chunks && (!ws || ws_bytes < medtok_embed_sequence_grad_workspace_bytes(batch, len, n_segments, width)))
         return fail("%s: workspace too small (%zu bytes given)", fn, ws_bytes);
@@ -1476,7 +1514,7 @@ extern "C" int medtok_embed_sequence_position_grad_f32(const float *g, const uin
     if (n_position_rows == 0) return 0;
     if (n_position_rows >= (1ll << 31)) return fail("%s: n_position_rows=%ld unsupported", fn, (long)n_position_rows);
     const int64_t total = n_position_rows * (int64_t)width;
-    if ((total + 255) / 256 > kSeqMaxBlocks) return fail("%s: %ld rows of %d exceed one launch", fn, (long)n_position_rows, width);
+    if ((total + 255) / 256 > kMaxBlocks) return fail("%s: %ld rows of %d exceed one launch", fn, (long)n_position_rows, width);
     if (!g_position || (batch > 0 && len > 0 && !g)) return fail("%s: g and g_position are required", fn);
     hipLaunchKernelGGL(embed_sequence_position_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, pad,
                        (long)batch, (long)len, (long)n_prefix, width, (long)total, g_position);
@@ -2530,33 +2568,51 @@ static bool code_grad_shape_ok(int64_t n, int slots, int topk, int64_t n_codes, 
            d > 0 && !(d & 3);
 }
 
-// What both gradients start with: the keys and their histogram, offsets[], first_chunk[] and the stable sort by row.  Returns which of
-// the two buffers holds the sorted payload.
-static int code_grad_sort(const CodeGradWs &w, const int64_t *index, const uint8_t *pad, int64_t n, const int64_t *tokens, int64_t num_codes,
-                          int slots, int topk, const DecodeRegions &reg, int64_t n_codes, bool narrow, hipStream_t s)
+// What both gradients are after their checks: the keys and their histogram, offsets[], first_chunk[] and the stable sort by row, then the
+// chunked sums of embed_grad_chunk_kernel<.., G_T, SLOT_BLOCKS> and the combine.  g is [n, slots * width] fp32 (SLOT_BLOCKS: the
+// upstream gradient of embed_codes' rows) or [n, width] in g_dtype (the upstream gradient of the folded lookup).
+template <bool SLOT_BLOCKS>
+static int embed_grad_sums(const char *fn, const void *g, int g_dtype, int64_t g_stride, const EmbedLookup &a, int64_t n, const DecodeRegions &reg,
+                           const CodeGradWs &w, float *G, float *bins, hipStream_t s)
 {
-    const long contributions = (long)n * slots * topk, items = (long)n * slots;
-    const int per = narrow ? 16 : 4;
-    hipLaunchKernelGGL(embed_code_grad_zero_kernel, dim3((unsigned)((n_codes + 255) / 256)), dim3(256), 0, s, w.counts, (long)n_codes);
-    if (narrow)
-        hipLaunchKernelGGL((embed_code_grad_keys_kernel<16>), dim3((unsigned)((items + per - 1) / per)), dim3(256), 0, s, index, pad, items, tokens,
-                           (long)num_codes, slots, topk, reg, (int)n_codes, w.keys[0], w.vals[0], w.counts);
-    else
-        hipLaunchKernelGGL((embed_code_grad_keys_kernel<64>), dim3((unsigned)((items + per - 1) / per)), dim3(256), 0, s, index, pad, items, tokens,
-                           (long)num_codes, slots, topk, reg, (int)n_codes, w.keys[0], w.vals[0], w.counts);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)n_codes, w.offsets);
-    hipLaunchKernelGGL(embed_code_grad_plan_kernel, dim3((unsigned)((n_codes + 255) / 256)), dim3(256), 0, s, w.counts, (long)n_codes);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)n_codes, w.first_chunk);
+    const long contributions = (long)n * a.slots * a.topk, items = (long)n * a.slots, rows = (long)a.rows, work = rows + w.extra;
+    hipLaunchKernelGGL(embed_code_grad_zero_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, w.counts, rows);
+    auto keys = [&](auto lanes) {
+        constexpr int per = 256 / decltype(lanes)::value;         // items per block
+        hipLaunchKernelGGL((embed_code_grad_keys_kernel<decltype(lanes)::value>), dim3((unsigned)((items + per - 1) / per)), dim3(256), 0, s, a.index,
+                           a.pad, items, a.tokens, (long)a.num_codes, a.slots, a.topk, reg, (int)rows, w.keys[0], w.vals[0], w.counts);
+    };
+    const bool narrow = item_lanes(a.width) == 16;
+    if (narrow) keys(std::integral_constant<int, 16>{}); else keys(std::integral_constant<int, 64>{});
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)rows, w.offsets);
+    hipLaunchKernelGGL(embed_code_grad_plan_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, w.counts, rows);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)rows, w.first_chunk);
     int cur = 0;
-    for (int shift = 0; shift == 0 || (n_codes >> shift); shift += 8) {       // keys lie in [0, n_codes]: the dead ones sort to the end
+    for (int shift = 0; shift == 0 || (rows >> shift); shift += 8) {         // keys lie in [0, rows]: the dead ones sort to the end
         hipLaunchKernelGGL((radix_count_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], contributions,
-                           (int)n_codes, shift, w.wave_counts);
+                           (int)rows, shift, w.wave_counts);
         hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.wave_counts, 256 * SORT_WAVES, w.wave_offsets);
         hipLaunchKernelGGL((radix_scatter_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], w.vals[cur],
-                           contributions, (int)n_codes, shift, w.wave_offsets, w.keys[cur ^ 1], w.vals[cur ^ 1]);
+                           contributions, (int)rows, shift, w.wave_offsets, w.keys[cur ^ 1], w.vals[cur ^ 1]);
         cur ^= 1;
     }
-    return cur;
+    auto chunks = [&](auto lanes, auto *typed) {                  // typed: a null pointer that carries the type of g
+        using G_T = std::remove_pointer_t<decltype(typed)>;
+        constexpr int per = 256 / decltype(lanes)::value;
+        hipLaunchKernelGGL((embed_grad_chunk_kernel<decltype(lanes)::value, G_T, SLOT_BLOCKS>), dim3((unsigned)((work + per - 1) / per)), dim3(256), 0,
+                           s, (const G_T *)g, (long)g_stride, a.index, a.weights, (long)a.num_codes, a.slots, a.topk, a.width, w.vals[cur], w.offsets,
+                           w.first_chunk, rows, w.extra, bins, G, w.chunk_sums);
+    };
+    auto by_type = [&](auto lanes) {
+        if constexpr (SLOT_BLOCKS) chunks(lanes, (float *)nullptr);
+        else if (g_dtype == MEDTOK_EMBED_G_F32) chunks(lanes, (float *)nullptr);
+        else if (g_dtype == MEDTOK_EMBED_G_F16) chunks(lanes, (_Float16 *)nullptr);
+        else chunks(lanes, (__bf16 *)nullptr);
+    };
+    if (narrow) by_type(std::integral_constant<int, 16>{}); else by_type(std::integral_constant<int, 64>{});
+    hipLaunchKernelGGL(embed_code_grad_combine_kernel, dim3((unsigned)lmin(4096, (rows + 3) / 4)), dim3(256), 0, s, w.chunk_sums, w.first_chunk, rows,
+                       a.width, G);
+    return check_launch(fn);
 }
 
 extern "C" size_t medtok_embed_code_grad_workspace_bytes(int64_t n, int slots, int topk, int64_t n_codes, int d)
@@ -2576,11 +2632,10 @@ extern "C" int medtok_embed_code_grad_f32(const float *g_out, int64_t g_stride, 
     if (n > ((1ll << 31) - 1) / (slots * topk))
         return fail("%s: n * slots * topk = %ld x %d x %d contributions reach 2^31 (the sort's payload is 32-bit): split the batch", fn, (long)n,
                     slots, topk);
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, nullptr, n_codes, d, region_lo, region_size};
     DecodeRegions reg;
-    if (int rc = decode_args(fn, n, slots, topk, n_codes, d, region_lo, region_size, reg)) return rc;
-    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
-    if (g_stride == 0) g_stride = (int64_t)slots * d;
-    if (g_stride < (int64_t)slots * d || (g_stride & 3)) return fail("%s: g_stride must be >= slots * d and a multiple of 4", fn);
+    if (int rc = embed_args(fn, a, n, false, reg)) return rc;
+    if (int rc = row_stride(fn, "g_stride", g_stride, (int64_t)slots * d, "slots * d")) return rc;
     if (!g_what || !bins) return fail("%s: g_what and bins are required", fn);
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
@@ -2589,43 +2644,16 @@ extern "C" int medtok_embed_code_grad_f32(const float *g_out, int64_t g_stride, 
         return 0;
     }
     if (!g_out || !index || !tokens || !weights) return fail("%s: g_out, index, tokens and weights are required", fn);
-    CodeGradWs w = code_grad_ws_layout(ws, (int64_t)n * slots * topk, n_codes, d);
+    const CodeGradWs w = code_grad_ws_layout(ws, (int64_t)n * slots * topk, n_codes, d);
     if (!ws || ws_bytes < w.total) return fail("%s: workspace too small (%zu < %zu)", fn, ws_bytes, w.total);
-    const bool narrow = d <= 64;
-    const int per = narrow ? 16 : 4;                              // items per block: 16 or 64 lanes each
-    const int cur = code_grad_sort(w, index, pad, n, tokens, num_codes, slots, topk, reg, n_codes, narrow, s);
-    const long work = (long)n_codes + w.extra;
-    if (narrow)
-        hipLaunchKernelGGL((embed_code_grad_chunk_kernel<16>), dim3((unsigned)((work + per - 1) / per)), dim3(256), 0, s, g_out, (long)g_stride, index,
-                           weights, (long)num_codes, slots, topk, d, w.vals[cur], w.offsets, w.first_chunk, (long)n_codes, w.extra, bins, g_what,
-                           w.chunk_sums);
-    else
-        hipLaunchKernelGGL((embed_code_grad_chunk_kernel<64>), dim3((unsigned)((work + per - 1) / per)), dim3(256), 0, s, g_out, (long)g_stride, index,
-                           weights, (long)num_codes, slots, topk, d, w.vals[cur], w.offsets, w.first_chunk, (long)n_codes, w.extra, bins, g_what,
-                           w.chunk_sums);
-    hipLaunchKernelGGL(embed_code_grad_combine_kernel, dim3((unsigned)lmin(4096, (n_codes + 3) / 4)), dim3(256), 0, s, w.chunk_sums, w.first_chunk,
-                       (long)n_codes, d, g_what);
-    return check_launch(fn);
+    return embed_grad_sums<true>(fn, g_out, MEDTOK_EMBED_G_F32, g_stride, a, n, reg, w, g_what, bins, s);
 }
 
-// ---- per-table-row sums of the folded lookup's upstream gradient (embed_table_grad_kernels.h): the same keys, sort, plan and combine
-#include "embed_table_grad_kernels.h"
-
+// ---- per-table-row sums of the folded lookup's upstream gradient: the same keys, sort, plan and combine
 extern "C" size_t medtok_embed_table_grad_workspace_bytes(int64_t n, int slots, int topk, int64_t table_rows, int hp)
 {
     if (!code_grad_shape_ok(n, slots, topk, table_rows, hp) || n > ((1ll << 31) - 1) / (slots * topk)) return 0;
     return code_grad_ws_layout(nullptr, n * slots * topk, table_rows, hp).total;
-}
-
-template <int LANES, typename G_T>
-static void table_grad_chunks(const void *g, int64_t g_stride, const int64_t *index, const float *weights, int64_t num_codes, int slots, int topk,
-                              int hp, const CodeGradWs &w, int cur, int64_t table_rows, float *bins, float *G, hipStream_t s)
-{
-    const int per = 256 / LANES;
-    const long work = (long)table_rows + w.extra;
-    hipLaunchKernelGGL((embed_table_grad_chunk_kernel<LANES, G_T>), dim3((unsigned)((work + per - 1) / per)), dim3(256), 0, s, (const G_T *)g,
-                       (long)g_stride, index, weights, (long)num_codes, slots, topk, hp, w.vals[cur], w.offsets, w.first_chunk, (long)table_rows,
-                       w.extra, bins, G, w.chunk_sums);
 }
 
 extern "C" int medtok_embed_table_grad(const void *g, int g_dtype, int64_t g_stride, const int64_t *index, const uint8_t *pad, int64_t n,
@@ -2645,11 +2673,10 @@ extern "C" int medtok_embed_table_grad(const void *g, int g_dtype, int64_t g_str
         return fail("%s: g_dtype=%d unsupported (MEDTOK_EMBED_G_F32, _F16 or _BF16)", fn, g_dtype);
     const CodeGradWs need = code_grad_ws_layout(nullptr, (int64_t)n * slots * topk, table_rows, hp);
     if (n > 0 && ws_bytes < need.total) return fail("%s: workspace too small (%zu < %zu)", fn, ws_bytes, need.total);
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, nullptr, table_rows, hp, row_offset, row_size};
     DecodeRegions reg;
-    if (int rc = decode_args(fn, n, slots, topk, table_rows, hp, row_offset, row_size, reg)) return rc;
-    if (num_codes < 1 || num_codes > (1ll << 40)) return fail("%s: num_codes=%ld unsupported", fn, (long)num_codes);
-    if (g_stride == 0) g_stride = hp;
-    if (g_stride < hp || (g_stride & 3)) return fail("%s: g_stride must be >= hp and a multiple of 4", fn);
+    if (int rc = embed_args(fn, a, n, false, reg)) return rc;
+    if (int rc = row_stride(fn, "g_stride", g_stride, hp, "hp")) return rc;
     if (!G || !bins) return fail("%s: G and bins are required", fn);
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
@@ -2660,16 +2687,7 @@ extern "C" int medtok_embed_table_grad(const void *g, int g_dtype, int64_t g_str
     if (!g || !index || !tokens || !weights || !ws) return fail("%s: g, index, tokens, weights and ws are required", fn);
     if (((uintptr_t)g & (g_dtype == MEDTOK_EMBED_G_F32 ? 15 : 7))) return fail("%s: g must be aligned to four of its elements", fn);
     const CodeGradWs w = code_grad_ws_layout(ws, (int64_t)n * slots * topk, table_rows, hp);
-    const bool narrow = hp <= 64;
-    const int cur = code_grad_sort(w, index, pad, n, tokens, num_codes, slots, topk, reg, table_rows, narrow, s);
-#define MEDTOK_TABLE_GRAD(L, T) table_grad_chunks<L, T>(g, g_stride, index, weights, num_codes, slots, topk, hp, w, cur, table_rows, bins, G, s)
-    if (g_dtype == MEDTOK_EMBED_G_F32) { if (narrow) MEDTOK_TABLE_GRAD(16, float); else MEDTOK_TABLE_GRAD(64, float); }
-    else if (g_dtype == MEDTOK_EMBED_G_F16) { if (narrow) MEDTOK_TABLE_GRAD(16, _Float16); else MEDTOK_TABLE_GRAD(64, _Float16); }
-    else { if (narrow) MEDTOK_TABLE_GRAD(16, __bf16); else MEDTOK_TABLE_GRAD(64, __bf16); }
-#undef MEDTOK_TABLE_GRAD
-    hipLaunchKernelGGL(embed_code_grad_combine_kernel, dim3((unsigned)lmin(4096, (table_rows + 3) / 4)), dim3(256), 0, s, w.chunk_sums, w.first_chunk,
-                       (long)table_rows, hp, G);
-    return check_launch(fn);
+    return embed_grad_sums<false>(fn, g, g_dtype, g_stride, a, n, reg, w, G, bins, s);
 }
 
 extern "C" size_t medtok_code_histogram_workspace_bytes(int64_t k_codes)

@@ -24,8 +24,7 @@ import torch.nn as nn
 
 from . import ops
 from .autograd import (_EmbedCodesFunction, _EmbedCodesTrainFunction, _EmbedPoolFunction, _EmbedProjectFunction,
-                       _EmbedProjectScatterFunction, _EmbedSequenceFunction, _EmbedSequenceRowsFunction, _EmbedSequenceScatterFunction,
-                       small_linear)
+                       _EmbedSequenceFunction, _EmbedSequenceRowsFunction, small_linear)
 
 DEFAULT_TYPES = ("text", "graph", "shared", "shared")
 
@@ -277,25 +276,16 @@ class MedTokEmbedding(nn.Module):
         if p is not None:
             if p.weight.dtype != torch.float32:
                 raise ValueError(f"MedTokEmbedding: the projector must be fp32 (every product behind the lookup is), got {p.weight.dtype}")
-            want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
-            unfolded = want_codebook and not self._scatter_trains()
-            norm = None if unfolded else q._normalised_codebook()
-            fold = False if unfolded else self.fold
-            if fold is None:
-                cache = self._fold_cache
-                fold = self.fold_rule(index.numel(), cache is not None and cache[0] == self._fold_key(norm))
+            want_codebook, _, norm, fold = self._route(grad_on, index.numel())
         status = torch.zeros(1, dtype=torch.int32, device=dev) if validate else None
         if fold:
             folded = self._folded(norm)
-            if self.grad_form == "scatter" and (parts_grad or want_codebook or (grad_on and any(
-                    t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb)))):
-                seq = _EmbedSequenceScatterFunction.apply(p.weight, p.bias, self.miss_emb, self._codebook_input() if want_codebook else None,
-                                                          position_rows, seg0, seg1, prefix, index, padding_mask, segment_id, self.tokens,
-                                                          self.weights, norm[0], tuple(regions), int(q.e_dim), folded, out_dtype, status)
-            elif parts_grad or (grad_on and any(t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb))):
-                seq = _EmbedSequenceFunction.apply(p.weight, p.bias, self.miss_emb, position_rows, seg0, seg1, prefix, index, padding_mask,
-                                                   segment_id, self.tokens, self.weights, norm[0], tuple(regions), int(q.e_dim), folded, out_dtype,
-                                                   status)
+            scatter = self.grad_form == "scatter"
+            if parts_grad or (scatter and want_codebook) or (grad_on and any(
+                    t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb))):
+                seq = _EmbedSequenceFunction.apply(p.weight, p.bias, self.miss_emb, self._codebook_input() if scatter and want_codebook else None,
+                                                   position_rows, seg0, seg1, prefix, index, padding_mask, segment_id, self.tokens, self.weights,
+                                                   norm[0], tuple(regions), int(q.e_dim), folded, out_dtype, status, scatter)
             else:
                 seq = ops.embed_sequence(index, self.tokens, self.weights, *folded[:3], miss_row=folded[3], pad_mask=padding_mask,
                                          position_rows=position_rows, segment_id=segment_id, segment_rows=terms or None, prefix=prefix,
@@ -408,6 +398,21 @@ class MedTokEmbedding(nn.Module):
             return False
         return bool(cache_valid) or positions * len(self.types) >= self.FOLD_COLD_FACTOR * rows
 
+    def _route(self, grad_on, positions):
+        """Which way a call with a projector goes -> (want_codebook, unfolded, norm, fold).  want_codebook: the codebook trains in this
+        call; unfolded: it does and the gradient form cannot serve it over the folded tables, so the lookup runs as it stands and the
+        dense product follows; norm: the normalised codebook (None where unfolded: the lookup makes its own, under autograd); fold: the
+        folded route is taken -- the module's setting, or fold_rule for this many positions."""
+        q = self.quantizer
+        want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
+        unfolded = want_codebook and not self._scatter_trains()
+        norm = None if unfolded else q._normalised_codebook()
+        fold = False if unfolded else self.fold
+        if fold is None:
+            cache = self._fold_cache
+            fold = self.fold_rule(positions, cache is not None and cache[0] == self._fold_key(norm))
+        return want_codebook, unfolded, norm, fold
+
     def _scatter_trains(self):
         """whether a codebook that trains may stay on the folded route: grad_form="scatter" (e_dim % 4 != 0 keeps the unfolded route)"""
         return self.grad_form == "scatter" and not getattr(self.quantizer, "_pad", 0)
@@ -442,13 +447,7 @@ class MedTokEmbedding(nn.Module):
         h, hp, n = p.out_features, ops.pad_dim(p.out_features), index.numel()
         padding_mask, out_dtype = self._checked(index, padding_mask, out_dtype, out, h)
         grad_on = out is None and torch.is_grad_enabled()
-        want_codebook = grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad
-        unfolded = want_codebook and not self._scatter_trains()
-        norm = None if unfolded else q._normalised_codebook()
-        fold = False if unfolded else self.fold
-        if fold is None:
-            cache = self._fold_cache
-            fold = self.fold_rule(n, cache is not None and cache[0] == self._fold_key(norm))
+        want_codebook, _, norm, fold = self._route(grad_on, n)
         if not fold:
             # the lookup (its own validation, miss-row and codebook gradients), then the dense product; `out` cannot take the fp32 rows
             with torch.set_grad_enabled(grad_on):                  # (a call that fills `out` is not differentiable: no graph is built)
@@ -462,13 +461,11 @@ class MedTokEmbedding(nn.Module):
         regions = self._regions()
         status = torch.zeros(1, dtype=torch.int32, device=self.tokens.device) if validate else None
         wants = [t is not None and t.requires_grad for t in (p.weight, p.bias, self.miss_emb)]
-        if self.grad_form == "scatter" and grad_on and (any(wants) or want_codebook):
-            res = _EmbedProjectScatterFunction.apply(p.weight, p.bias, self.miss_emb, self._codebook_input() if want_codebook else None, index,
-                                                     padding_mask, self.tokens, self.weights, norm[0], tuple(regions), int(q.e_dim), folded,
-                                                     out_dtype, status)
-        elif grad_on and any(wants):
-            res = _EmbedProjectFunction.apply(p.weight, p.bias, self.miss_emb, index, padding_mask, self.tokens, self.weights, norm[0],
-                                              tuple(regions), int(q.e_dim), folded, out_dtype, status)
+        scatter = self.grad_form == "scatter"
+        if grad_on and (any(wants) or (scatter and want_codebook)):
+            res = _EmbedProjectFunction.apply(p.weight, p.bias, self.miss_emb, self._codebook_input() if scatter and want_codebook else None, index,
+                                              padding_mask, self.tokens, self.weights, norm[0], tuple(regions), int(q.e_dim), folded, out_dtype,
+                                              status, scatter)
         else:
             res = ops.embed_project(index, self.tokens, self.weights, *folded[:3], miss_row=folded[3], pad_mask=padding_mask,
                                     out=out if hp == h else None, out_dtype=out_dtype, status=status)

@@ -374,6 +374,14 @@ def _embed_mask_on_device(pad_mask):
     return pad_mask.view(torch.uint8) if pad_mask.dtype == torch.bool else pad_mask
 
 
+def _embed_miss(fn, miss, width):
+    """the miss row of embed_codes / embed_pool: None, or fp32 [width] or [1, width]"""
+    if miss is not None and (not isinstance(miss, torch.Tensor) or miss.dtype != torch.float32 or miss.numel() != width or miss.dim() not in (1, 2)
+                             or miss.shape[-1] != width):
+        raise ValueError(f"{fn}: miss must be fp32 [{width}] or [1, {width}], got {getattr(miss, 'dtype', type(miss))} "
+                         f"{tuple(getattr(miss, 'shape', ()))}")
+
+
 def embed_codes(index, tokens, weights, what, regions=None, miss=None, pad_mask=None, out=None, out_dtype=torch.float32, status=None):
     """Embeddings of code indices straight from the stored token table: what `table[index]` gives over the table
     decode_tokens(tokens, weights, ...) would build (plus a miss row), in one launch and without the table -> [*index.shape, slots * d].
@@ -397,10 +405,7 @@ def embed_codes(index, tokens, weights, what, regions=None, miss=None, pad_mask=
         raise ValueError(f"{fn}: the token table is empty")
     d = what.shape[1]
     n, width = index.numel(), s * d
-    if miss is not None and (not isinstance(miss, torch.Tensor) or miss.dtype != torch.float32 or miss.numel() != width or miss.dim() not in (1, 2)
-                             or miss.shape[-1] != width):
-        raise ValueError(f"{fn}: miss must be fp32 [{width}] or [1, {width}], got {getattr(miss, 'dtype', type(miss))} "
-                         f"{tuple(getattr(miss, 'shape', ()))}")
+    _embed_miss(fn, miss, width)
     if out is not None:
         align = 16 if out_dtype == torch.float32 else 8
         if not (isinstance(out, torch.Tensor) and out.dtype == out_dtype and tuple(out.shape) == (n, width) and out.stride(1) == 1
@@ -455,6 +460,22 @@ def embed_codes_miss_grad(g_out, index, num_codes, pad_mask=None):
 EMBED_CODE_GRAD_CHUNK = 256                 # contributions per fmaf chain of embed_codes_code_grad (MEDTOK_EMBED_CODE_GRAD_CHUNK: part of the bits)
 
 
+def _embed_grad_prepare(fn, index, tokens, weights, regions, pad_mask, g, g_name):
+    """What embed_codes_code_grad and embed_project_table_grad do between their shape checks and the call: the bound of the sort's 32-bit payload, then index, lists and mask
+    as device tensors, g checked to be one, and the regions as C arrays -> (index, tokens, weights, pad_mask, lo[], size[])"""
+    n, (_, s, k) = index.numel(), tokens.shape
+    if n * s * k >= 1 << 31:
+        raise ValueError(f"{fn}: {n} positions x {s} slots x {k} ids reach 2^31 contributions (the sort's payload is 32-bit): split the batch")
+    index = _dev(index, "index", torch.int64)
+    tokens, weights = _dev(tokens, "tokens", torch.int64), _dev(weights, "weights")
+    pad_mask = _embed_mask_on_device(pad_mask)
+    if not g.is_cuda:
+        _dev(g, g_name, g.dtype)
+    import ctypes as C
+    arr = C.c_int64 * s
+    return index, tokens, weights, pad_mask, arr(*[r[0] for r in regions]), arr(*[r[1] for r in regions])
+
+
 def embed_codes_code_grad(g_out, index, tokens, weights, what_shape_or_what, regions=None, pad_mask=None):
     """Gradient of embed_codes w.r.t. the NORMALISED codebook, straight from the upstream gradient -> (g_what [n_codes, d], bins [n_codes]).
 
@@ -487,19 +508,10 @@ def embed_codes_code_grad(g_out, index, tokens, weights, what_shape_or_what, reg
             or g_out.numel() != n * width):
         raise ValueError(f"{fn}: g_out must be a floating [*{tuple(index.shape)}, {width}] tensor, got {getattr(g_out, 'dtype', type(g_out))} "
                          f"{tuple(getattr(g_out, 'shape', ()))}")
-    if n * s * k >= 1 << 31:
-        raise ValueError(f"{fn}: {n} positions x {s} slots x {k} ids reach 2^31 contributions (the sort's payload is 32-bit): split the batch")
-    index = _dev(index, "index", torch.int64)
-    tokens, weights = _dev(tokens, "tokens", torch.int64), _dev(weights, "weights")
-    pad_mask = _embed_mask_on_device(pad_mask)
-    if not g_out.is_cuda:
-        _dev(g_out, "g_out", g_out.dtype)
+    index, tokens, weights, pad_mask, los, sizes = _embed_grad_prepare(fn, index, tokens, weights, regions, pad_mask, g_out, "g_out")
     g_out = g_out.reshape(n, width).float()
     if n and not (g_out.stride(1) == 1 and g_out.stride(0) >= width and g_out.stride(0) % 4 == 0 and g_out.data_ptr() % 16 == 0):
         g_out = g_out.contiguous()
-    import ctypes as C
-    arr = C.c_int64 * s
-    los, sizes = arr(*[r[0] for r in regions]), arr(*[r[1] for r in regions])
     lib = _lib.load()
     dev = g_out.device
     g_what = torch.empty((n_codes, d), dtype=torch.float32, device=dev)
@@ -552,19 +564,10 @@ def embed_project_table_grad(g, index, tokens, weights, row_regions, pad_mask=No
     num_codes, s, k = tokens.shape
     if num_codes < 1:
         raise ValueError(f"{fn}: the token table is empty")
-    if n * s * k >= 1 << 31:
-        raise ValueError(f"{fn}: {n} positions x {s} slots x {k} ids reach 2^31 contributions (the sort's payload is 32-bit): split the batch")
-    index = _dev(index, "index", torch.int64)
-    tokens, weights = _dev(tokens, "tokens", torch.int64), _dev(weights, "weights")
-    pad_mask = _embed_mask_on_device(pad_mask)
-    if not g.is_cuda:
-        _dev(g, "g", g.dtype)
+    index, tokens, weights, pad_mask, los, sizes = _embed_grad_prepare(fn, index, tokens, weights, row_regions, pad_mask, g, "g")
     g = g.reshape(n, hp)
     if n and not (g.stride(1) == 1 and g.stride(0) >= hp and g.stride(0) * g.element_size() % 16 == 0 and g.data_ptr() % 16 == 0):
         g = g.contiguous()
-    import ctypes as C
-    arr = C.c_int64 * s
-    los, sizes = arr(*[r[0] for r in row_regions]), arr(*[r[1] for r in row_regions])
     lib = _lib.load()
     dev = g.device
     G = torch.empty((rows, hp), dtype=torch.float32, device=dev)
@@ -608,10 +611,7 @@ def embed_pool(index, tokens, weights, what, regions=None, miss=None, pad_mask=N
     width = s * d
     if s * k > 64 or width > EMBED_POOL_MAX_WIDTH:
         raise ValueError(f"{fn}: {s} slots x {k} ids (at most 64 entries per code) and rows of {width} floats (at most {EMBED_POOL_MAX_WIDTH}) unsupported")
-    if miss is not None and (not isinstance(miss, torch.Tensor) or miss.dtype != torch.float32 or miss.numel() != width or miss.dim() not in (1, 2)
-                             or miss.shape[-1] != width):
-        raise ValueError(f"{fn}: miss must be fp32 [{width}] or [1, {width}], got {getattr(miss, 'dtype', type(miss))} "
-                         f"{tuple(getattr(miss, 'shape', ()))}")
+    _embed_miss(fn, miss, width)
     index = _dev(index, "index", torch.int64)
     tokens, weights, what, los, sizes = _decode_on_device(tokens, weights, what, regions)
     miss = None if miss is None else _dev(miss, "miss")
@@ -705,6 +705,42 @@ def fold_projector(what, regions, W, b=None, miss=None, e_dim=None):
     return table, row_regions, bias, miss_row
 
 
+def _folded_shapes(fn, index, index_dims, tokens, weights, table, row_regions, bias, miss_row, pad_mask, out_dtype, width=None):
+    """The ValueError half of embed_project / embed_sequence (index_dims = 2: index must be [batch, length]): types and shapes of the
+    index, the mask, the stored lists against the folded tables, the bias and the miss row -> (pad_mask, tokens [num_codes, s, k],
+    weights, row_regions, width); nothing is moved or loaded.  width: the width of embed_sequence's additive tensors (default: the tables')."""
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+    if index_dims is not None and index.dim() != index_dims:
+        raise ValueError(f"{fn}: index must be [batch, length], got {tuple(index.shape)}")
+    if out_dtype not in EMBED_OUT_DTYPES:
+        raise ValueError(f"{fn}: out_dtype must be one of {EMBED_OUT_DTYPES}, got {out_dtype!r}")
+    pad_mask = _embed_mask(fn, pad_mask, index)
+    tokens, weights, row_regions = _decode_shapes(fn, tokens, weights, table, row_regions)
+    num_codes, s, k = tokens.shape
+    if num_codes < 1:
+        raise ValueError(f"{fn}: the token table is empty")
+    if s * k > 64:
+        raise ValueError(f"{fn}: {s} slots of {k} ids are more than the 64 entries per code the kernel takes")
+    hp = table.shape[1]
+    width = hp if width is None else int(width)
+    if pad_dim(width) != hp:
+        raise ValueError(f"{fn}: width = {width} does not pad to the tables' {hp} columns")
+    for name, t in (("bias", bias), ("miss_row", miss_row)):
+        if (t is not None or name == "bias") and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (hp,)):
+            raise ValueError(f"{fn}: {name} must be fp32 [{hp}], got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    return pad_mask, tokens, weights, row_regions, width
+
+
+def _folded_on_device(index, tokens, weights, table, row_regions, bias, miss_row, pad_mask):
+    """the device half: contiguous device tensors (MedTokLibraryError for anything else) and the regions as C arrays"""
+    index = _dev(index, "index", torch.int64)
+    tokens, weights, table, los, sizes = _decode_on_device(tokens, weights, table, row_regions)
+    bias = _dev(bias, "bias")
+    miss_row = None if miss_row is None else _dev(miss_row, "miss_row")
+    return index, tokens, weights, table, los, sizes, bias, miss_row, _embed_mask_on_device(pad_mask)
+
+
 def embed_project(index, tokens, weights, table, row_regions, bias, miss_row=None, pad_mask=None, out=None, out_dtype=torch.float32,
                   status=None):
     """projector(embed_codes(index, ...)) in one launch, without the [positions, slots * d] activation: the lookup over the folded
@@ -716,32 +752,18 @@ def embed_project(index, tokens, weights, table, row_regions, bias, miss_row=Non
     other index outside [0, num_codes) gives the bias row and sets bit 4 of `status`; a slot with an id outside its region contributes
     nothing and sets bit s -- nothing is read back here.  `out`: a [index.numel(), Hp] device view of out_dtype with unit column stride."""
     fn = "embed_project"
-    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
-        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
-    if out_dtype not in EMBED_OUT_DTYPES:
-        raise ValueError(f"{fn}: out_dtype must be one of {EMBED_OUT_DTYPES}, got {out_dtype!r}")
-    pad_mask = _embed_mask(fn, pad_mask, index)
-    tokens, weights, row_regions = _decode_shapes(fn, tokens, weights, table, row_regions)
+    pad_mask, tokens, weights, row_regions, _ = _folded_shapes(fn, index, None, tokens, weights, table, row_regions, bias, miss_row, pad_mask,
+                                                               out_dtype)
     num_codes, s, k = tokens.shape
-    if num_codes < 1:
-        raise ValueError(f"{fn}: the token table is empty")
-    if s * k > 64:
-        raise ValueError(f"{fn}: {s} slots of {k} ids are more than the 64 entries per code the kernel takes")
     hp = table.shape[1]
     n = index.numel()
-    for name, t in (("bias", bias), ("miss_row", miss_row)):
-        if (t is not None or name == "bias") and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (hp,)):
-            raise ValueError(f"{fn}: {name} must be fp32 [{hp}], got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
     if out is not None:
         align = 16 if out_dtype == torch.float32 else 8
         if not (isinstance(out, torch.Tensor) and out.dtype == out_dtype and tuple(out.shape) == (n, hp) and out.stride(1) == 1
                 and out.stride(0) % 4 == 0 and out.data_ptr() % align == 0):
             raise ValueError(f"{fn}: out must be a {out_dtype} [{n}, {hp}] view with unit column stride and {align}-byte aligned rows")
-    index = _dev(index, "index", torch.int64)
-    tokens, weights, table, los, sizes = _decode_on_device(tokens, weights, table, row_regions)
-    bias = _dev(bias, "bias")
-    miss_row = None if miss_row is None else _dev(miss_row, "miss_row")
-    pad_mask = _embed_mask_on_device(pad_mask)
+    index, tokens, weights, table, los, sizes, bias, miss_row, pad_mask = _folded_on_device(index, tokens, weights, table, row_regions, bias, miss_row,
+                                                                                           pad_mask)
     if out is not None and not out.is_cuda:
         _dev(out, "out", out_dtype)
     if status is not None:
@@ -835,34 +857,15 @@ def embed_sequence(index, tokens, weights, table, row_regions, bias, miss_row=No
     here).  A g outside [0, V) adds no segment term and sets bit EMBED_BAD_SEGMENT_BIT of `status`; a miss position and a bad code index
     take the adds like any unpadded position.  Nothing is read back here."""
     fn = "embed_sequence"
-    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
-        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
-    if index.dim() != 2:
-        raise ValueError(f"{fn}: index must be [batch, length], got {tuple(index.shape)}")
-    if out_dtype not in EMBED_OUT_DTYPES:
-        raise ValueError(f"{fn}: out_dtype must be one of {EMBED_OUT_DTYPES}, got {out_dtype!r}")
-    pad_mask = _embed_mask(fn, pad_mask, index)
-    tokens, weights, row_regions = _decode_shapes(fn, tokens, weights, table, row_regions)
+    pad_mask, tokens, weights, row_regions, width = _folded_shapes(fn, index, 2, tokens, weights, table, row_regions, bias, miss_row, pad_mask,
+                                                                   out_dtype, width)
     num_codes, s, k = tokens.shape
-    if num_codes < 1:
-        raise ValueError(f"{fn}: the token table is empty")
-    if s * k > 64:
-        raise ValueError(f"{fn}: {s} slots of {k} ids are more than the 64 entries per code the kernel takes")
     hp = table.shape[1]
-    width = hp if width is None else int(width)
-    if pad_dim(width) != hp:
-        raise ValueError(f"{fn}: width = {width} does not pad to the tables' {hp} columns")
-    for name, t in (("bias", bias), ("miss_row", miss_row)):
-        if (t is not None or name == "bias") and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (hp,)):
-            raise ValueError(f"{fn}: {name} must be fp32 [{hp}], got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
     batch, length = index.shape
     parts = _sequence_parts(fn, batch, length, width, position_rows, segment_id, segment_rows, prefix)
     n_segments, n_prefix = parts[4:]
-    index = _dev(index, "index", torch.int64)
-    tokens, weights, table, los, sizes = _decode_on_device(tokens, weights, table, row_regions)
-    bias = _dev(bias, "bias")
-    miss_row = None if miss_row is None else _dev(miss_row, "miss_row")
-    pad_mask = _embed_mask_on_device(pad_mask)
+    index, tokens, weights, table, los, sizes, bias, miss_row, pad_mask = _folded_on_device(index, tokens, weights, table, row_regions, bias, miss_row,
+                                                                                           pad_mask)
     position_rows, segment_id, terms, prefix = _sequence_parts_on_device(*parts[:4], columns=hp - width)
     if status is not None:
         status = _dev(status, "status", torch.int32)

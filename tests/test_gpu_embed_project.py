@@ -1,5 +1,5 @@
 """GPU: MedTokEmbedding with a projector -- the consumers' nn.Linear folded into the lookup (ops.fold_projector / ops.embed_project,
-embed_project_kernel) -- against torch fp64, against the unfolded path, and under autograd.
+embed_folded_kernel) -- against torch fp64, against the unfolded path, and under autograd.
 
 Bar: rel() <= 1e-5 of the output's scale, the RTOL and rel() of tests/test_gpu_embed.py and tests/test_gpu_decode.py; the existing
 fp32 composition F.linear(module(index, mask), W, b) must meet it on the same inputs, so the inputs are known to be fair.  Half

@@ -1,5 +1,5 @@
 """GPU: MedTokEmbedding.sequence -- the consumer's input sequence (lookup + position rows + segment rows behind prefix rows) in the
-lookup's launch (ops.embed_sequence, embed_sequence_kernel) or, where the lookup does not run over folded tables, in one elementwise
+lookup's launch (ops.embed_sequence, embed_folded_kernel) or, where the lookup does not run over folded tables, in one elementwise
 launch over its fp32 rows (ops.embed_sequence_rows) -- and the gradients of the additive parts.
 
 The comparator is the composition a user writes today, in torch on the module's own `forward`:

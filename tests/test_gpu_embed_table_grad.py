@@ -1,5 +1,5 @@
 """GPU: the scatter form of the folded lookup's gradients -- ops.embed_project_table_grad (medtok_embed_table_grad,
-embed_table_grad_chunk_kernel) and MedTokEmbedding(grad_form="scatter").
+embed_grad_chunk_kernel) and MedTokEmbedding(grad_form="scatter").
 
 The kernel is compared bit for bit with ops.embed_codes_code_grad on the upstream gradient tiled once per slot (the same contribution
 order and chunking; that function is pinned to its host restatement in tests/test_gpu_embed_code_grad.py).  Module gradients are
