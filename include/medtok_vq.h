@@ -363,6 +363,41 @@ int medtok_embed_pool_f32(const int64_t *index, const uint8_t *pad, int64_t bags
                           int64_t out_stride, int *counts, int *status, void *ws, size_t ws_bytes, void *stream);
 int medtok_embed_pool_miss_grad_f32(const float *g_out, int64_t g_stride, const int *counts, int64_t bags, int width, float *g_acc,
                                     void *ws, size_t ws_bytes, void *stream);
+/* Segment pooling: one row per (batch row, segment) -- the visit-level sequence of an EHR transformer (the reference's patientEncoder_old
+ * runs over [B, max_visit_num, dim] visit embeddings, EHRModel_token.py:249-292) without the [batch, len, slots * d] rows.  index,
+ * segment_id int64 [batch, len], pad [batch, len] or NULL (non-zero = padded, any pattern); V = n_segments.  Bag (b, v) is the unpadded
+ * positions p of batch row b with segment_id[b, p] == v, in any order and not necessarily contiguous along the row.  With row(p) and n(v)
+ * as medtok_embed_pool_f32:
+ *   out[b * V + v] = ( sum over the bag's positions, in the fixed order given below, of n(row(b, p)) ) / (float)count[b, v]
+ * An empty bag is a row of zeros.  A padded position reads neither its index nor its segment id.  An unpadded position whose segment id
+ * is outside [0, V) joins no bag and sets bit MEDTOK_EMBED_BAD_SEGMENT_BIT of *status; a position with a bad code index counts in its bag
+ * as a row of zeros (bit 4).  No segment id, index or token id forms an address before it has been checked; address products are 64-bit.
+ * The fixed order (part of the result's bits):
+ *   1. a bag's list is its positions in ascending p;
+ *   2. the list is cut into chunks of MEDTOK_EMBED_POOL_CHUNK = 16 entries;
+ *   3. inside a chunk the arithmetic is medtok_embed_pool_f32's: entry j belongs to wavefront j % 4, each wavefront adds its entries in
+ *      ascending order, and the four wavefronts are added ((w0 + w1) + w2) + w3;
+ *   4. the chunk sums are added in chunk order from +0;
+ *   5. the result is divided by (float)count (a true division).
+ * So with V = 1, every id 0 and no mask, out is bit for bit medtok_embed_pool_f32's.  No float atomics: the bits depend on (index,
+ * segment_id, pad, the tables) only.  The lists are made by an integer histogram, a scan and a stable radix sort of (bag, position) keys;
+ * every step is a kernel launch and nothing is read back, so the call can be recorded into a graph.
+ * out fp32 [batch * V, out_stride] (0 = slots * d, a multiple of 4); counts int32 [batch * V, 2] = (count, the bag's miss positions): what
+ * medtok_embed_pool_miss_grad_f32 takes with bags = batch * V.  ws from the workspace query, host arithmetic on its four arguments, each
+ * part rounded up to 256 bytes: 12 bytes per bag (the histogram, offsets[bags + 1], first_chunk[bags + 1]), the sort's digit tables
+ * (2 x 65,536 counters + 1), 16 bytes per position (two key and two payload buffers), and Q = ceil(2 * batch * len / 16) partial rows of
+ * width floats with their (count, miss) pairs -- a bound on the chunks of the bags longer than one chunk; shorter bags have no partial
+ * row.  The query returns 0 for batch == 0 and for an unsupported shape.  Errors named as such, reported before any pointer is looked at
+ * and before anything is launched: batch * len >= 2^31, batch * V + 1 >= 2^31, V < 1, slots * topk > 64, slots * d >
+ * MEDTOK_EMBED_POOL_MAX_WIDTH, batch * V + Q beyond the 2^24 - 1 blocks of one launch, a workspace that is too small. */
+#define MEDTOK_EMBED_POOL_CHUNK 16
+#define MEDTOK_EMBED_POOL_MAX_WIDTH 4096
+size_t medtok_embed_pool_segments_workspace_bytes(int64_t batch, int64_t len, int64_t n_segments, int width);
+int medtok_embed_pool_segments_f32(const int64_t *index, const uint8_t *pad, const int64_t *segment_id, int64_t batch, int64_t len,
+                                   int64_t n_segments, const int64_t *tokens, const float *weights, int64_t num_codes, int slots, int topk,
+                                   const float *what, int64_t n_codes, int d, const int64_t *region_lo, const int64_t *region_size,
+                                   const float *miss, int normalize, float *out, int64_t out_stride, int *counts, int *status, void *ws,
+                                   size_t ws_bytes, void *stream);
 /* The consumer's input sequence in the lookup's launch: what the EHR model builds between `projector(med_code_emb[index])` and its first
  * transformer layer (EHRModel_token.py:220-232, PositionalEncoding.forward :65-78): a positional row per position, two time rows per
  * position carried from the position's visit, and the (cls, gender, ethnicity) rows in front.  index, pad [batch, len]; out

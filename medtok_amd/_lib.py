@@ -85,6 +85,9 @@ SIGNATURES = {
     "medtok_embed_pool_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "medtok_embed_pool_f32": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _int, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "medtok_embed_pool_miss_grad_f32": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
+    "medtok_embed_pool_segments_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
+    "medtok_embed_pool_segments_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _int, _vp,
+                                              _i64, _vp, _vp, _vp, _sz, _vp]),
     "medtok_embed_sequence_f32": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                          _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "medtok_embed_sequence_f16": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _int, _int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,

@@ -591,29 +591,58 @@ class _EmbedCodesTrainFunction(torch.autograd.Function):
 
 
 class _EmbedPoolFunction(torch.autograd.Function):
-    """MedTokEmbedding.pooled with a frozen codebook under autograd: the pooling kernels (medtok_embed_pool_f32), whose one
+    """MedTokEmbedding.pooled and .pooled_segments with a frozen codebook under autograd: the pooling kernels (medtok_embed_pool_f32, or
+    medtok_embed_pool_segments_f32 where segment_id is given: a bag per (batch row, segment), out [B, V, width]), whose one
     differentiable input is the miss row (the table is a constant).  Every unpadded miss position of bag b adds n(miss) / live_b to
     pooled[b], so backward is G = sum_b (miss_b / live_b) g[b] in bag order (medtok_embed_pool_miss_grad_f32: fixed order, no float
     atomics, two runs give the same bits) and, with normalisation, G taken through n by ops.normalize_backward."""
 
     @staticmethod
-    def forward(ctx, miss, index, pad_mask, tokens, weights, what, regions, normalize, status):
-        out, counts = ops.embed_pool(index, tokens, weights, what, regions, miss=miss.detach(), pad_mask=pad_mask, normalize=normalize,
-                                     status=status)
+    def forward(ctx, miss, index, pad_mask, tokens, weights, what, regions, normalize, status, segment_id=None, n_segments=0):
+        if segment_id is None:
+            out, counts = ops.embed_pool(index, tokens, weights, what, regions, miss=miss.detach(), pad_mask=pad_mask, normalize=normalize,
+                                         status=status)
+        else:
+            out, counts = ops.embed_pool_segments(index, segment_id, n_segments, tokens, weights, what, regions, miss=miss.detach(),
+                                                  pad_mask=pad_mask, normalize=normalize, status=status)
+            ctx.mark_non_differentiable(counts)
         ctx.save_for_backward(miss, counts)
         ctx.normalize = bool(normalize)
-        return out
+        return out if segment_id is None else (out, counts)
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, *_):
         miss, counts = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
-            return (None,) * 9
-        g_acc = ops.embed_pool_miss_grad(g, counts)
+            return (None,) * 11
+        g_acc = ops.embed_pool_miss_grad(g.reshape(-1, g.shape[-1]), counts.reshape(-1, 2))
         if ctx.normalize:
             v = miss.detach().reshape(1, -1).contiguous()
             g_acc = ops.normalize_backward(g_acc.view(1, -1), torch.nn.functional.normalize(v, dim=-1), v)
-        return (g_acc.reshape(miss.shape),) + (None,) * 8
+        return (g_acc.reshape(miss.shape),) + (None,) * 10
+
+
+class _SegmentSumFunction(torch.autograd.Function):
+    """sums[b, v] = the sum of rows[b, p] over the unpadded p with segment_id[b, p] == v, rows fp32 [B, L, W] -> [B, V, W]: the composed
+    route of MedTokEmbedding.pooled_segments (a training codebook).  Forward is the fixed-order ops.embed_sequence_segment_grad (no float
+    atomics, V <= ops.EMBED_SEQ_MAX_SEGMENTS); backward is the masked gather g[b, segment_id[b, p]] (zeros at padded positions and at ids
+    outside [0, V))."""
+
+    @staticmethod
+    def forward(ctx, rows, segment_id, n_segments, pad_mask):
+        ctx.save_for_backward(segment_id, pad_mask)
+        ctx.n_segments = int(n_segments)
+        return ops.embed_sequence_segment_grad(rows.detach(), segment_id, n_segments, pad_mask)
+
+    @staticmethod
+    def backward(ctx, g):
+        segment_id, pad_mask = ctx.saved_tensors
+        on = (segment_id >= 0) & (segment_id < ctx.n_segments)
+        if pad_mask is not None:
+            on = on & (pad_mask == 0)
+        at = torch.where(on, segment_id, torch.zeros_like(segment_id))
+        rows = torch.gather(g, 1, at.unsqueeze(-1).expand(-1, -1, g.shape[-1]))
+        return rows * on.unsqueeze(-1).to(rows.dtype), None, None, None
 
 
 class _SmallLinearFunction(torch.autograd.Function):

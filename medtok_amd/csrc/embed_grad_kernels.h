@@ -86,13 +86,15 @@ __global__ __launch_bounds__(256) void embed_code_grad_zero_kernel(int *__restri
     if (r < k_codes) counts[r] = 0;
 }
 
-// in place: counts[r] -> the number of chunks of row r where it has more than one, else 0
+// in place: counts[r] -> the number of chunks of row r where it has more than one, else 0 (CHUNK: MEDTOK_EMBED_CODE_GRAD_CHUNK here,
+// MEDTOK_EMBED_POOL_CHUNK for the bags of embed_pool_segments_kernels.h)
+template <int CHUNK>
 __global__ __launch_bounds__(256) void embed_code_grad_plan_kernel(int *__restrict__ counts, long k_codes)
 {
     const long r = (long)blockIdx.x * 256 + threadIdx.x;
     if (r >= k_codes) return;
     const int len = counts[r];
-    counts[r] = len > MEDTOK_EMBED_CODE_GRAD_CHUNK ? (len + MEDTOK_EMBED_CODE_GRAD_CHUNK - 1) / MEDTOK_EMBED_CODE_GRAD_CHUNK : 0;
+    counts[r] = len > CHUNK ? (len + CHUNK - 1) / CHUNK : 0;
 }
 
 template <int LANES, typename G_T, bool SLOT_BLOCKS>

@@ -331,22 +331,72 @@ __global__ __launch_bounds__(256) void embed_folded_kernel(const int64_t *__rest
 //
 // embed_pool_finish_kernel adds a bag's partial rows in chunk order from +0, divides by (float)live_b (a true division; live_b == 0:
 // zeros) and writes out[bag, :] and counts[bag] = (live_b, miss_b).
-#define MEDTOK_EMBED_POOL_CHUNK 16
+// (MEDTOK_EMBED_POOL_CHUNK = 16 and MEDTOK_EMBED_POOL_MAX_WIDTH = 4096 come from include/medtok_vq.h: the chunk is part of the result's bits)
 #define MEDTOK_EMBED_POOL_TURNS (MEDTOK_EMBED_POOL_CHUNK / 4)
-#define MEDTOK_EMBED_POOL_MAX_WIDTH 4096
 
-template <int R, int MAXK>
+//
+// LISTED: a bag is a LIST of positions instead of a row of index (MedTokEmbedding.pooled_segments: "the unpadded positions of row b whose
+// segment is v"; embed_pool_segments_kernels.h makes the lists).  Bag g's list is sorted[offsets[g] .. offsets[g + 1]), flat positions in
+// ascending order, cut into chunks of MEDTOK_EMBED_POOL_CHUNK entries; entry j of a chunk stands where position chunk * 16 + j of the bag
+// stands above, and everything behind the position -- index and id validation, gathers, the chain, the norm, the wavefront sum, the order
+// -- is the code above.  No mask is read (a listed position is unpadded).  The grid is the plan of embed_grad_chunk_kernel: blocks
+// [0, bags) are the bags, and a bag of at most one chunk is FINISHED by its block (0 + the chunk's sum, divided by (float)count -- the
+// arithmetic of embed_pool_finish_kernel over one chunk; an empty bag: zeros; counts[bag] = (count, miss positions)), so the many short
+// or empty bags have no partial row; blocks [bags, bags + extra) are the chunks of the longer bags: block bags + q finds its bag by
+// bisection in first_chunk[] and writes partial[q] and chunk_counts[q].  A block with nothing to do returns before its first barrier.
+// Without LISTED nothing of this exists in the instantiation and `list` is not looked at (one argument list serves both): the figures
+// above are unchanged.  With LISTED, VGPRs / waves per SIMD -- <1, 8> 70 / 7, <1, 16> 74 / 6, <4, 8> 98 / 4, <4, 16> 100 / 4, <12, 8>
+// 162 / 3, <12, 16> 164 / 3, <16, 8> 194 / 2, <16, 16> 196 / 2; no AGPRs, no scratch, no spills.
+struct EmbedPoolList {
+    const uint32_t *sorted;          // [positions] flat positions b * L + p, sorted by bag, ascending inside a bag
+    const int *offsets;              // [bags + 1]
+    const int *first_chunk;          // [bags + 1]: the first partial row of a bag with several chunks
+    long bags, extra;                // B * V, and the bound on the chunks of the longer bags
+    float *out;                      // [bags, out_stride]
+    long out_stride;
+    int *counts;                     // [bags, 2]
+};
+
+template <int R, int MAXK, bool LISTED>
 __global__ __launch_bounds__(256) void embed_pool_partial_kernel(const int64_t *__restrict__ index, const uint8_t *__restrict__ pad, long bag_len,
                                                                  int chunks, const int64_t *__restrict__ tokens, const float *__restrict__ weights,
                                                                  long num_codes, int slots, int topk, const float *__restrict__ what, int d,
                                                                  DecodeRegions reg, const float *__restrict__ miss, int normalize,
-                                                                 float *__restrict__ partial, int *__restrict__ chunk_counts, int *status)
+                                                                 float *__restrict__ partial, int *__restrict__ chunk_counts, int *status,
+                                                                 EmbedPoolList list)
 {
     extern __shared__ float4 pool_row[];                          // width / 4 float4: the running sum over the wavefronts
     __shared__ int wave_live[4], wave_miss[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long bag = (long)blockIdx.x / chunks;
-    const int chunk = (int)((long)blockIdx.x - bag * chunks);
+    long bag, row = (long)blockIdx.x;                             // row: where this block's sum and counts go in partial / chunk_counts
+    int chunk;
+    [[maybe_unused]] int first = 0, cnt = 0;                      // LISTED: this chunk is sorted[first .. first + cnt)
+    [[maybe_unused]] bool whole = false;                          // LISTED: the chunk is the whole bag, finished here
+    if constexpr (LISTED) {
+        chunk = 0;
+        if (row < list.bags) {
+            bag = row;
+            first = list.offsets[bag];
+            cnt = list.offsets[bag + 1] - first;
+            if (cnt > MEDTOK_EMBED_POOL_CHUNK) return;            // its chunks are further blocks (uniform over the block)
+            whole = true;
+        } else {
+            row -= list.bags;
+            if (row >= list.first_chunk[list.bags]) return;       // (uniform over the block)
+            long a = 0, b = list.bags - 1;                        // the bag g with first_chunk[g] <= row < first_chunk[g + 1]
+            while (a < b) {
+                const long mid = (a + b) >> 1;
+                if (list.first_chunk[mid + 1] > row) b = mid; else a = mid + 1;
+            }
+            bag = a;
+            first = list.offsets[a] + ((int)row - list.first_chunk[a]) * MEDTOK_EMBED_POOL_CHUNK;
+            const int left = list.offsets[a + 1] - first;
+            cnt = left < MEDTOK_EMBED_POOL_CHUNK ? left : MEDTOK_EMBED_POOL_CHUNK;
+        }
+    } else {
+        bag = row / chunks;
+        chunk = (int)(row - bag * chunks);
+    }
     const int width = slots * d, entries = slots * topk;         // entries <= 64, width <= 256 R (checked on the host)
     const int eslot = lane / topk;                                // the slot of this lane's entry
     long lo = reg.lo[0], size = reg.size[0];
@@ -366,9 +416,16 @@ __global__ __launch_bounds__(256) void embed_pool_partial_kernel(const int64_t *
 #pragma unroll
     for (int t = 0; t < MEDTOK_EMBED_POOL_TURNS; ++t) {
         const long p = (long)chunk * MEDTOK_EMBED_POOL_CHUNK + t * 4 + wave;
-        const bool in = p < bag_len;
-        const long gp = bag * bag_len + (in ? p : 0);
-        const bool padded = !in || (pad && pad[gp] != 0);
+        bool in;
+        long gp;
+        if constexpr (LISTED) {
+            in = p < cnt;
+            gp = in ? (long)list.sorted[first + p] : 0;           // < B * L: the keys kernel wrote its own position
+        } else {
+            in = p < bag_len;
+            gp = bag * bag_len + (in ? p : 0);
+        }
+        const bool padded = !in || (!LISTED && pad && pad[gp] != 0);
         const long c = padded ? 0 : index[gp];
         const bool is_code = !padded && c >= 0 && c < num_codes;
         const bool is_miss = !padded && miss && c == num_codes;
@@ -472,7 +529,10 @@ __global__ __launch_bounds__(256) void embed_pool_partial_kernel(const int64_t *
         }
     }
     if (lane == 0) { wave_live[wave] = live; wave_miss[wave] = missed; }
-    float *dst = partial + (long)blockIdx.x * width;
+    float *dst = partial + row * width;
+    if constexpr (LISTED) {
+        if (whole) dst = list.out + bag * list.out_stride;
+    }
 #pragma unroll 1
     for (int w = 0; w < 4; ++w) {                                 // ((w0 + w1) + w2) + w3: a lane meets its own columns only
         if (wave == w) {
@@ -485,6 +545,16 @@ __global__ __launch_bounds__(256) void embed_pool_partial_kernel(const int64_t *
                     const float4 b = pool_row[q];
                     a.x = b.x + a.x; a.y = b.y + a.y; a.z = b.z + a.z; a.w = b.w + a.w;
                 }
+                if constexpr (LISTED) {
+                    if (w == 3 && whole) {                        // embed_pool_finish_kernel over this one chunk: from +0, then the division
+                        if (cnt > 0) {
+                            const float n = (float)cnt;
+                            a.x = (0.f + a.x) / n; a.y = (0.f + a.y) / n; a.z = (0.f + a.z) / n; a.w = (0.f + a.w) / n;
+                        } else {
+                            a = make_float4(0.f, 0.f, 0.f, 0.f);
+                        }
+                    }
+                }
                 if (w < 3) pool_row[q] = a;
                 else st4(dst + q * 4, a);
             }
@@ -492,17 +562,28 @@ __global__ __launch_bounds__(256) void embed_pool_partial_kernel(const int64_t *
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        chunk_counts[2 * (long)blockIdx.x] = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
-        chunk_counts[2 * (long)blockIdx.x + 1] = wave_miss[0] + wave_miss[1] + wave_miss[2] + wave_miss[3];
+        int *to = chunk_counts + 2 * row;
+        if constexpr (LISTED) {
+            if (whole) to = list.counts + 2 * bag;
+        }
+        to[0] = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
+        to[1] = wave_miss[0] + wave_miss[1] + wave_miss[2] + wave_miss[3];
     }
 }
 
-// grid = (bags, ceil(width / 1024)); a thread owns one float4 column of one bag
+// grid = (bags, ceil(width / 1024)); a thread owns one float4 column of one bag.  first_chunk (the LISTED form of the partial kernel):
+// a bag's partial rows are [first_chunk[bag], first_chunk[bag + 1]); a bag without any was finished by the partial kernel and is left alone.
 __global__ __launch_bounds__(256) void embed_pool_finish_kernel(const float *__restrict__ partial, const int *__restrict__ chunk_counts, int chunks,
-                                                                int width, float *__restrict__ out, long out_stride, int *__restrict__ counts)
+                                                                int width, float *__restrict__ out, long out_stride, int *__restrict__ counts,
+                                                                const int *__restrict__ first_chunk)
 {
     __shared__ int bag_live;
-    const long first = (long)blockIdx.x * chunks;                 // the bag's first chunk
+    long first = (long)blockIdx.x * chunks;                       // the bag's first chunk
+    if (first_chunk) {
+        first = first_chunk[blockIdx.x];
+        chunks = first_chunk[blockIdx.x + 1] - (int)first;
+        if (chunks == 0) return;                                  // (uniform over the block)
+    }
     if (threadIdx.x == 0) {                                       // one thread adds the chunks' counts (integers: any order), the block reads the sum
         int live_sum = 0, missed = 0;
         for (int ch = 0; ch < chunks; ++ch) {

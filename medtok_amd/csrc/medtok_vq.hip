@@ -12,6 +12,7 @@
 //   embed_kernels.h       code indices -> stored tokens -> embedding; the folded lookup, also as the consumer's input sequence; the pool
 //   embed_sequence_kernels.h  the input sequence over dense rows, and the additive rows' gradients
 //   embed_grad_kernels.h  the codebook's and the folded tables' gradient through the lookup: sort keys, chunked per-row sums
+//   embed_pool_segments_kernels.h  the pool with a bag per (batch row, segment): the keys of the positions' lists
 //   train_kernels.h       sparse backward, normalize backward, InfoNCE
 //   loss_kernels.h        alignment / orthogonality losses
 //   attention_*.h         ragged cross-attention cores (fp32, fp16 x 3, LDS-DMA, two-tile, e_dim = 64) and their backward
@@ -1311,12 +1312,12 @@ extern "C" int medtok_embed_pool_f32(const int64_t *index, const uint8_t *pad, i
     const int per_lane = width <= 256 ? 1 : width <= 1024 ? 4 : width <= 3072 ? 12 : 16;
     if (blocks)
         dispatch_group<1, 4, 12, 16>(per_lane, topk, [&](auto r, auto maxk) {
-            hipLaunchKernelGGL((embed_pool_partial_kernel<decltype(r)::value, decltype(maxk)::value>), dim3((unsigned)blocks), dim3(256),
+            hipLaunchKernelGGL((embed_pool_partial_kernel<decltype(r)::value, decltype(maxk)::value, false>), dim3((unsigned)blocks), dim3(256),
                                (size_t)width * sizeof(float), s, index, pad, (long)bag_len, (int)chunks, tokens, weights, (long)num_codes, slots,
-                               topk, what, d, reg, miss, normalize, partial, chunk_counts, status);
+                               topk, what, d, reg, miss, normalize, partial, chunk_counts, status, EmbedPoolList{});
         });
     hipLaunchKernelGGL(embed_pool_finish_kernel, dim3((unsigned)bags, (unsigned)((width + 1023) / 1024)), dim3(256), 0, s, (const float *)partial,
-                       (const int *)chunk_counts, (int)chunks, width, out, (long)out_stride, counts);
+                       (const int *)chunk_counts, (int)chunks, width, out, (long)out_stride, counts, (const int *)nullptr);
     return check_launch(fn);
 }
 
@@ -2585,7 +2586,7 @@ static int embed_grad_sums(const char *fn, const void *g, int g_dtype, int64_t g
     const bool narrow = item_lanes(a.width) == 16;
     if (narrow) keys(std::integral_constant<int, 16>{}); else keys(std::integral_constant<int, 64>{});
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)rows, w.offsets);
-    hipLaunchKernelGGL(embed_code_grad_plan_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, w.counts, rows);
+    hipLaunchKernelGGL(embed_code_grad_plan_kernel<MEDTOK_EMBED_CODE_GRAD_CHUNK>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, w.counts, rows);
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)rows, w.first_chunk);
     int cur = 0;
     for (int shift = 0; shift == 0 || (rows >> shift); shift += 8) {         // keys lie in [0, rows]: the dead ones sort to the end
@@ -2688,6 +2689,108 @@ extern "C" int medtok_embed_table_grad(const void *g, int g_dtype, int64_t g_str
     if (((uintptr_t)g & (g_dtype == MEDTOK_EMBED_G_F32 ? 15 : 7))) return fail("%s: g must be aligned to four of its elements", fn);
     const CodeGradWs w = code_grad_ws_layout(ws, (int64_t)n * slots * topk, table_rows, hp);
     return embed_grad_sums<false>(fn, g, g_dtype, g_stride, a, n, reg, w, G, bins, s);
+}
+
+// ---- segment pooling: a row per (batch row, segment) -- the keys, the sort above, then the pool's kernels over listed positions
+#include "embed_pool_segments_kernels.h"
+
+struct PoolSegmentsWs {
+    int *counts, *offsets, *first_chunk, *wave_counts, *wave_offsets;
+    uint32_t *keys[2], *vals[2];
+    float *partial;
+    int *chunk_counts;
+    long extra;                 // Q: the bound on the chunks of bags with several
+    size_t total;
+};
+
+// everything from (B, L, V, width): nothing here depends on the data
+static PoolSegmentsWs pool_segments_ws_layout(void *ws, int64_t n, int64_t bags, int width)
+{
+    PoolSegmentsWs w;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *p = ws ? (char *)ws + off : nullptr; off += align_up(bytes, 256); return (void *)p; };
+    w.counts = (int *)take((size_t)bags * 4);                     // the histogram, then (in place) the bags' chunk counts
+    w.offsets = (int *)take((size_t)(bags + 1) * 4);
+    w.first_chunk = (int *)take((size_t)(bags + 1) * 4);
+    w.wave_counts = (int *)take((size_t)256 * SORT_WAVES * 4);
+    w.wave_offsets = (int *)take(((size_t)256 * SORT_WAVES + 1) * 4);
+    for (int i = 0; i < 2; ++i) { w.keys[i] = (uint32_t *)take((size_t)n * 4); w.vals[i] = (uint32_t *)take((size_t)n * 4); }
+    w.extra = (long)((2 * n + MEDTOK_EMBED_POOL_CHUNK - 1) / MEDTOK_EMBED_POOL_CHUNK);
+    w.partial = (float *)take((size_t)w.extra * (size_t)width * sizeof(float));
+    w.chunk_counts = (int *)take((size_t)w.extra * 2 * sizeof(int));
+    w.total = off;
+    return w;
+}
+
+// the limits of one call, in the order they are reported; nullptr: supported
+static const char *pool_segments_limit(int64_t batch, int64_t len, int64_t n_segments, int64_t width)
+{
+    if (batch < 0 || len < 0) return "batch and len must be >= 0";
+    if (n_segments < 1) return "n_segments must be >= 1";
+    if (batch > 0 && len > ((1ll << 31) - 1) / batch) return "batch * len positions reach 2^31 (the sort's payload is 32-bit): split the batch";
+    if (batch > 0 && n_segments > ((1ll << 31) - 2) / batch) return "batch * n_segments + 1 bags reach 2^31 (the sort's keys are 32-bit): split the batch";
+    if (width < 1) return "width must be >= 1";
+    if (width > MEDTOK_EMBED_POOL_MAX_WIDTH) return "rows of slots * d floats exceed MEDTOK_EMBED_POOL_MAX_WIDTH";
+    return nullptr;
+}
+
+extern "C" size_t medtok_embed_pool_segments_workspace_bytes(int64_t batch, int64_t len, int64_t n_segments, int width)
+{
+    if (pool_segments_limit(batch, len, n_segments, width) || batch == 0) return 0;
+    return pool_segments_ws_layout(nullptr, batch * len, batch * n_segments, width).total;
+}
+
+extern "C" int medtok_embed_pool_segments_f32(const int64_t *index, const uint8_t *pad, const int64_t *segment_id, int64_t batch, int64_t len,
+                                              int64_t n_segments, const int64_t *tokens, const float *weights, int64_t num_codes, int slots,
+                                              int topk, const float *what, int64_t n_codes, int d, const int64_t *region_lo,
+                                              const int64_t *region_size, const float *miss, int normalize, float *out, int64_t out_stride,
+                                              int *counts, int *status, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "embed_pool_segments";
+    if (slots >= 1 && topk >= 1 && (int64_t)slots * topk > 64)
+        return fail("%s: slots * topk = %ld entries per code exceed one wavefront", fn, (long)slots * topk);
+    if (const char *why = pool_segments_limit(batch, len, n_segments, slots >= 1 && d >= 1 ? (int64_t)slots * d : 1))
+        return fail("%s: %s (batch=%ld len=%ld n_segments=%ld slots=%d d=%d)", fn, why, (long)batch, (long)len, (long)n_segments, slots, d);
+    const int64_t n = batch * len, bags = batch * n_segments;
+    const EmbedLookup a = {index, pad, tokens, weights, num_codes, slots, topk, what, n_codes, d, region_lo, region_size};
+    DecodeRegions reg;
+    if (int rc = embed_args(fn, a, n, true, reg)) return rc;
+    const int width = slots * d;
+    if (int rc = row_stride(fn, "out_stride", out_stride, width, "slots * d")) return rc;
+    if (batch == 0) return 0;
+    const PoolSegmentsWs w = pool_segments_ws_layout(ws, n, bags, width);
+    if (bags + w.extra > kMaxBlocks)
+        return fail("%s: %ld bags + %ld chunks exceed one launch (%ld blocks of 256 threads)", fn, (long)bags, (long)w.extra, (long)kMaxBlocks);
+    if (!ws || ws_bytes < w.total) return fail("%s: workspace too small (%zu bytes given, %zu needed)", fn, ws_bytes, w.total);
+    if (!tokens || !weights || !what || !out || !counts || (n > 0 && (!index || !segment_id)))
+        return fail("%s: index, segment_id, tokens, weights, what, out and counts are required", fn);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(embed_code_grad_zero_kernel, dim3((unsigned)((bags + 255) / 256)), dim3(256), 0, s, w.counts, (long)bags);
+    if (n > 0)
+        hipLaunchKernelGGL(embed_pool_segments_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pad, segment_id, (long)n, (long)len,
+                           (long)n_segments, (uint32_t)bags, w.keys[0], w.vals[0], w.counts, status);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)bags, w.offsets);
+    hipLaunchKernelGGL(embed_code_grad_plan_kernel<MEDTOK_EMBED_POOL_CHUNK>, dim3((unsigned)((bags + 255) / 256)), dim3(256), 0, s, w.counts, (long)bags);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int)bags, w.first_chunk);
+    int cur = 0;
+    for (int shift = 0; n > 0 && (shift == 0 || (bags >> shift)); shift += 8) {          // keys lie in [0, bags]: the dead ones sort to the end
+        hipLaunchKernelGGL((radix_count_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], (long)n, 0, shift,
+                           w.wave_counts);
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.wave_counts, 256 * SORT_WAVES, w.wave_offsets);
+        hipLaunchKernelGGL((radix_scatter_kernel<false>), dim3(SORT_BLOCKS), dim3(256), 0, s, (const int64_t *)nullptr, w.keys[cur], w.vals[cur],
+                           (long)n, 0, shift, w.wave_offsets, w.keys[cur ^ 1], w.vals[cur ^ 1]);
+        cur ^= 1;
+    }
+    const EmbedPoolList list = {w.vals[cur], w.offsets, w.first_chunk, (long)bags, w.extra, out, (long)out_stride, counts};
+    const int per_lane = width <= 256 ? 1 : width <= 1024 ? 4 : width <= 3072 ? 12 : 16;
+    dispatch_group<1, 4, 12, 16>(per_lane, topk, [&](auto r, auto maxk) {
+        hipLaunchKernelGGL((embed_pool_partial_kernel<decltype(r)::value, decltype(maxk)::value, true>), dim3((unsigned)(bags + w.extra)), dim3(256),
+                           (size_t)width * sizeof(float), s, index, (const uint8_t *)nullptr, 0l, 0, tokens, weights, (long)num_codes, slots, topk,
+                           what, d, reg, miss, normalize, w.partial, w.chunk_counts, status, list);
+    });
+    hipLaunchKernelGGL(embed_pool_finish_kernel, dim3((unsigned)bags, (unsigned)((width + 1023) / 1024)), dim3(256), 0, s, (const float *)w.partial,
+                       (const int *)w.chunk_counts, 0, width, out, (long)out_stride, counts, (const int *)w.first_chunk);
+    return check_launch(fn);
 }
 
 extern "C" size_t medtok_code_histogram_workspace_bytes(int64_t k_codes)

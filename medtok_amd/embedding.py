@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import ops
 from .autograd import (_EmbedCodesFunction, _EmbedCodesTrainFunction, _EmbedPoolFunction, _EmbedProjectFunction,
-                       _EmbedSequenceFunction, _EmbedSequenceRowsFunction, small_linear)
+                       _EmbedSequenceFunction, _EmbedSequenceRowsFunction, _SegmentSumFunction, small_linear)
 
 DEFAULT_TYPES = ("text", "graph", "shared", "shared")
 
@@ -318,7 +318,8 @@ class MedTokEmbedding(nn.Module):
 
             pooled[b] = (sum over the unpadded p of bag b, in a fixed order, of n(row(p))) / live_b,     n(v) = v / max(|v|_2, 1e-12)
 
-        The norm runs over the whole row (all slots), not per slot; normalize=False: n(v) = v.  padding_mask: bool / uint8 [B, L],
+        The norm runs over the whole row (all slots), not per slot; normalize=False: n(v) = v (the default here is True, the QA
+        adapter's form; pooled_segments, the EHR form, defaults to False).  padding_mask: bool / uint8 [B, L],
         True = padded, any pattern (not only a prefix); padded positions are not read.  live_b counts the unpadded positions: a
         position with a bad index counts (validate=False: as a row of zeros).  Deviation from the reference: a bag without an unpadded
         position is a row of ZEROS (the reference's mean over an empty set is NaN); a row of norm 0 contributes zeros.  The sum has a
@@ -353,7 +354,8 @@ class MedTokEmbedding(nn.Module):
                 miss = (torch.nn.functional.pad(miss.view(s, e), (0, pad)) if pad else miss).reshape(-1)
             status = torch.zeros(1, dtype=torch.int32, device=self.tokens.device) if validate else None
             if want_miss:
-                res = _EmbedPoolFunction.apply(miss, index, padding_mask, self.tokens, self.weights, what, tuple(regions), bool(normalize), status)
+                res = _EmbedPoolFunction.apply(miss, index, padding_mask, self.tokens, self.weights, what, tuple(regions), bool(normalize), status,
+                                               None, 0)
             else:
                 res = ops.embed_pool(index, self.tokens, self.weights, what, regions, miss=miss, pad_mask=padding_mask, normalize=normalize,
                                      status=status)[0]
@@ -376,6 +378,107 @@ class MedTokEmbedding(nn.Module):
             keep = (padding_mask.to(rows.device) == 0).float()
         live = keep.sum(1, keepdim=True)
         return torch.where(live > 0, (rows * keep.unsqueeze(-1)).sum(1) / live.clamp(min=1.0), torch.zeros_like(live))
+
+    # ------------------------------------------------------------------ a row per visit
+    def pooled_segments(self, index, segment_id, n_segments, padding_mask=None, normalize: bool = False, validate: bool = True):
+        """index, segment_id int64 [B, L] -> (out fp32 [B, V, S * e_dim], empty bool [B, V]), V = n_segments: one row per (batch row,
+        segment) -- the mean of `forward`'s rows over the unpadded positions of row b whose segment id is v -- in one pass and without the
+        [B, L, S * e_dim] rows (ops.embed_pool_segments).  With the dataloader's visit_id[:, :, 0] as segment_id this is the visit-level
+        input of the reference's patientEncoder_old (EHRModel_token.py:249-272: a transformer over [B, max_visit_num, dim] visit embeddings),
+        and `empty` is its src_key_padding_mask (the sense of pad_sequence's mask, :279-292: True where there is no visit):
+
+            out[b, v] = (sum over the unpadded p with segment_id[b, p] == v, in a fixed order, of n(row(b, p))) / count[b, v]
+
+        n(v) = v / max(|v|_2, 1e-12) over the whole row with normalize=True, else v.  normalize defaults to False here: the EHR path
+        never normalises, and `sequence` does not either (`pooled`, the QA adapter's form, defaults to True).  padding_mask: bool / uint8
+        [B, L], True = padded, any pattern; a padded position reads neither its index nor its segment id.  Segment ids may come in any
+        order along a row (ascending runs are the dataloader's form) and need not be contiguous.  An empty (b, v) is a row of zeros.  A
+        position with a bad code index counts towards its segment as a row of zeros (validate=False), as in `pooled`; an unpadded
+        position whose segment id is outside [0, V) joins no segment.  The order is fixed (include/medtok_vq.h: positions ascending,
+        chunks of ops.EMBED_POOL_CHUNK summed as `pooled` sums a chunk, chunk sums in order from +0, a true division) and there are no
+        float atomics: two calls give the same bits, relabelling the segments permutes the rows bit for bit, with V = 1, every id 0 and
+        no mask out[:, 0] is `pooled`'s, and with normalize=False a segment of one position holds that position's `forward` row.
+
+        validate=True reads ONE status word back and raises the ValueErrors of `forward` first ("code index", then the first slot with a
+        bad id), then `sequence`'s, naming the "segment id"; validate=False reads nothing, and every step is a kernel launch, so the call
+        -- forward and backward -- can be captured in a HIP graph.  With a frozen codebook the only gradient is miss_emb's (`pooled`'s
+        arithmetic over B * V bags; two backward runs give the same bits).  freeze_codebook=False composes the result from `forward`'s
+        rows, F.normalize, the fixed-order per-segment sum of ops.embed_sequence_segment_grad (V <= ops.EMBED_SEQ_MAX_SEGMENTS on this
+        route) and a division by integer counts: the [B, L, S * e_dim] rows exist on that route.
+
+        With a projector the result is projector(out) [B, V, H] by the exact fp32 dense product on the B * V pooled rows (an empty
+        segment: the bias row, as in `pooled`).  The projector is not folded into the tables here."""
+        name = "MedTokEmbedding.pooled_segments"
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+            raise ValueError(f"MedTokEmbedding: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+        if index.dim() != 2:
+            raise ValueError(f"{name} takes index [B, L], got {tuple(index.shape)}")
+        batch, length = index.shape
+        if not isinstance(segment_id, torch.Tensor) or segment_id.dtype != torch.int64 or segment_id.shape != index.shape:
+            raise ValueError(f"{name}: segment_id must be an int64 [{batch}, {length}] tensor, got {getattr(segment_id, 'dtype', type(segment_id))} "
+                             f"{tuple(getattr(segment_id, 'shape', ()))}")
+        n_segments = int(n_segments)
+        if n_segments < 1:
+            raise ValueError(f"{name}: n_segments = {n_segments} must be >= 1")
+        padding_mask = ops._embed_mask("MedTokEmbedding", padding_mask, index)
+        q = self.quantizer
+        s, e, pad = len(self.types), int(q.e_dim), getattr(q, "_pad", 0)
+        grad_on = torch.is_grad_enabled()
+        regions = self._regions()
+        if grad_on and not self.freeze_codebook and q.codebook.weight.requires_grad:
+            res, empty = self._pooled_segments_composed(index, segment_id, n_segments, padding_mask, normalize, validate)
+        else:
+            what = q._normalised_codebook()[0]
+            miss = self.miss_emb
+            want_miss = grad_on and miss is not None and miss.requires_grad
+            if miss is not None:
+                if not want_miss:
+                    miss = miss.detach()
+                miss = (torch.nn.functional.pad(miss.view(s, e), (0, pad)) if pad else miss).reshape(-1)
+            status = torch.zeros(1, dtype=torch.int32, device=self.tokens.device) if validate else None
+            if want_miss:
+                res, counts = _EmbedPoolFunction.apply(miss, index, padding_mask, self.tokens, self.weights, what, tuple(regions), bool(normalize),
+                                                       status, segment_id, n_segments)
+            else:
+                res, counts = ops.embed_pool_segments(index, segment_id, n_segments, self.tokens, self.weights, what, regions, miss=miss,
+                                                      pad_mask=padding_mask, normalize=normalize, status=status)
+            if pad:                                               # (the padding columns are zeros: they change no norm)
+                res = res.reshape(batch, n_segments, s, e + pad)[..., :e].reshape(batch, n_segments, s * e)
+            empty = counts[..., 0] == 0
+            if validate:
+                self._raise_on_segments(int(status.item()), regions, n_segments)
+        p = getattr(self, "projector", None)
+        if p is not None:
+            res = small_linear(res.reshape(batch * n_segments, -1), p.weight, p.bias).reshape(batch, n_segments, -1)
+        return res, empty
+
+    def _raise_on_segments(self, word, regions, n_segments):
+        """`forward`'s two errors first, then `sequence`'s "segment id" error"""
+        self._raise_on(word & ~(1 << ops.EMBED_BAD_SEGMENT_BIT), regions)
+        if word >> ops.EMBED_BAD_SEGMENT_BIT & 1:
+            raise ValueError(f"MedTokEmbedding: a segment id outside [0, {n_segments}) at a position the padding mask does not cover")
+
+    def _pooled_segments_composed(self, index, segment_id, n_segments, padding_mask, normalize, validate):
+        """freeze_codebook=False: the same function from the lookup's rows (_lookup: the kernel forward, ops.embed_codes_code_grad
+        backward), torch's normalise, the fixed-order per-segment sum (_SegmentSumFunction) and integer counts made in torch, so that
+        codebook.weight gets its gradient.  No index_add_."""
+        rows = self._lookup(index, padding_mask, validate, torch.float32, None)
+        if normalize:
+            rows = torch.nn.functional.normalize(rows, dim=-1)
+        segment_id = segment_id.to(rows.device)
+        mask = None if padding_mask is None else padding_mask.to(rows.device)
+        on = (segment_id >= 0) & (segment_id < n_segments)
+        if mask is not None:
+            on = on & (mask == 0)
+            if validate and bool(((mask == 0) & ~on).any()):
+                raise ValueError(f"MedTokEmbedding: a segment id outside [0, {n_segments}) at a position the padding mask does not cover")
+        elif validate and not bool(on.all()):
+            raise ValueError(f"MedTokEmbedding: a segment id outside [0, {n_segments}) at a position the padding mask does not cover")
+        sums = _SegmentSumFunction.apply(rows, segment_id, n_segments, mask)
+        hit = torch.arange(n_segments, device=rows.device).view(1, 1, -1) == torch.where(on, segment_id, -1).unsqueeze(-1)   # [B, L, V]
+        count = hit.sum(1)                                                                                                   # integers
+        empty = count == 0
+        return torch.where(empty.unsqueeze(-1), torch.zeros_like(sums), sums / count.clamp(min=1).unsqueeze(-1).float()), empty
 
     # ------------------------------------------------------------------ the projector behind the lookup
     def fold_table_shape(self):

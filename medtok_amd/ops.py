@@ -656,6 +656,66 @@ def embed_pool_miss_grad(g_out, counts):
     return g_acc
 
 
+def embed_pool_segments(index, segment_id, n_segments, tokens, weights, what, regions=None, miss=None, pad_mask=None, normalize: bool = False,
+                        status=None):
+    """embed_pool with a bag per (batch row, segment): (out fp32 [B, V, slots * d], counts int32 [B, V, 2]), V = n_segments.
+
+    index, segment_id int64 [B, L]; tokens, weights, what, regions, miss, status: as embed_codes; pad_mask: bool / uint8 [B, L], True =
+    padded, any pattern.  Bag (b, v) is the unpadded positions p of row b with segment_id[b, p] == v (ids in any order along the row, not
+    necessarily contiguous), and with row(p), n(v) as embed_pool
+        out[b, v] = (sum over the bag, in a fixed order, of n(row(b, p))) / count[b, v]
+    An empty bag is a row of zeros; counts[b, v] = (count, the bag's miss positions): what embed_pool_miss_grad takes as
+    counts.reshape(B * V, 2).  A padded position reads neither its index nor its segment id; an unpadded id outside [0, V) joins no bag
+    and sets bit EMBED_BAD_SEGMENT_BIT of `status`; a bad code index counts in its bag as a row of zeros (bit EMBED_BAD_INDEX_BIT).
+    The order (include/medtok_vq.h): a bag's positions ascending, chunks of EMBED_POOL_CHUNK entries summed as embed_pool sums a chunk,
+    chunk sums in chunk order from +0, a true division -- no float atomics, two runs give the same bits, and with V = 1, ids 0 and no
+    mask the result is embed_pool's bit for bit.  normalize defaults to False here (embed_pool: True).
+    slots * k <= 64, slots * d <= EMBED_POOL_MAX_WIDTH, B * L < 2^31, B * V + 1 < 2^31.  Every step is a kernel launch and nothing is read back."""
+    fn = "embed_pool_segments"
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"{fn}: index must be an int64 tensor, got {getattr(index, 'dtype', type(index))}")
+    if index.dim() != 2:
+        raise ValueError(f"{fn}: index must be [batch, length], got {tuple(index.shape)}")
+    batch, length = index.shape
+    if not isinstance(segment_id, torch.Tensor) or segment_id.dtype != torch.int64 or segment_id.shape != index.shape:
+        raise ValueError(f"{fn}: segment_id must be an int64 [{batch}, {length}] tensor, got {getattr(segment_id, 'dtype', type(segment_id))} "
+                         f"{tuple(getattr(segment_id, 'shape', ()))}")
+    n_segments = int(n_segments)
+    if n_segments < 1:
+        raise ValueError(f"{fn}: n_segments = {n_segments} must be >= 1")
+    if batch * length >= 1 << 31:
+        raise ValueError(f"{fn}: {batch} x {length} positions reach 2^31: split the batch")
+    if batch * n_segments + 1 >= 1 << 31:
+        raise ValueError(f"{fn}: {batch} x {n_segments} segments + 1 reach 2^31: split the batch")
+    pad_mask = _embed_mask(fn, pad_mask, index)
+    tokens, weights, regions = _decode_shapes(fn, tokens, weights, what, regions)
+    num_codes, s, k = tokens.shape
+    if num_codes < 1:
+        raise ValueError(f"{fn}: the token table is empty")
+    d = what.shape[1]
+    width = s * d
+    if s * k > 64 or width > EMBED_POOL_MAX_WIDTH:
+        raise ValueError(f"{fn}: {s} slots x {k} ids (at most 64 entries per code) and rows of {width} floats (at most {EMBED_POOL_MAX_WIDTH}) unsupported")
+    _embed_miss(fn, miss, width)
+    index = _dev(index, "index", torch.int64)
+    segment_id = _dev(segment_id, "segment_id", torch.int64)
+    tokens, weights, what, los, sizes = _decode_on_device(tokens, weights, what, regions)
+    miss = None if miss is None else _dev(miss, "miss")
+    pad_mask = _embed_mask_on_device(pad_mask)
+    if status is not None:
+        status = _dev(status, "status", torch.int32)
+    out = torch.empty((batch, n_segments, width), dtype=torch.float32, device=what.device)
+    counts = torch.empty((batch, n_segments, 2), dtype=torch.int32, device=what.device)
+    lib = _lib.load()
+    ws = _ws(lib.medtok_embed_pool_segments_workspace_bytes(batch, length, n_segments, width), what)
+    with _on(what.device):
+        _lib.check(lib.medtok_embed_pool_segments_f32(index.data_ptr(), _ptr(pad_mask), segment_id.data_ptr(), batch, length, n_segments,
+                                                      tokens.data_ptr(), weights.data_ptr(), num_codes, s, k, what.data_ptr(), what.shape[0], d,
+                                                      los, sizes, _ptr(miss), int(bool(normalize)), out.data_ptr(), width, counts.data_ptr(),
+                                                      _ptr(status), ws.data_ptr(), ws.numel(), _stream(what)), "medtok_embed_pool_segments_f32")
+    return out, counts
+
+
 def fold_projector(what, regions, W, b=None, miss=None, e_dim=None):
     """The consumer's projector applied to the codebook instead of to every position: what embed_project gathers from.
 

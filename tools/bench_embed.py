@@ -68,6 +68,22 @@ row; compared before anything is timed (fp32: bit for bit at the unpadded positi
 `spread` of a case = (ms_max - ms_min) / ms_median over its samples.  The result goes under the key "sequence" of --out (the other keys
 are kept).
 
+--segments: one row per visit (MedTokEmbedding.pooled_segments: the mean of `forward`'s rows over the unpadded positions of each (batch
+row, visit); the input of the reference's patientEncoder_old, EHRModel_token.py:249-292) at the --sequence shape -- --batch 256 --length
+2000, --visits 100, the reference store shape, no projector, normalize=False -- with the visit ids in ascending runs along a row (the
+dataloader's form) and, as a second case, the same ids shuffled along the row; compared at the timed size before anything is timed (1e-5
+of the result's scale, and the `empty` masks equal):
+
+  pooled_segments            module.pooled_segments(index, segment_id, V, mask, validate=False): keys, sort, pooling over listed positions
+  composition_segment_grad   what a user writes today without atomics: module(index, mask, validate=False) rows [B, L, S * e_dim], then
+                             ops.embed_sequence_segment_grad(rows, segment_id, V, mask) / the counts
+  composition_index_add      the same rows, then zeros(B * V + 1, W).index_add_(0, b * V + id, rows) / the counts (float atomics: the
+                             bits change from run to run)
+
+Per side the timing statistics, `spread` and `peak_bytes` (the rise of torch.cuda.max_memory_allocated() over one call); per case
+`pooled_segments_not_slower_within_spread` against each composition: the fused median <= the composition's median + (its max - its
+min).  The result goes under the key "segments" of --out (the other keys are kept).
+
 --grad-form (with --project H or --sequence H): forward + backward of the folded route with MedTokEmbedding(grad_form="scatter") against
 grad_form="dense" (the parent commit's arithmetic unchanged), both modules over one projector and one miss row, from a fixed upstream
 gradient; outputs (bit for bit) and gradients (1e-5 of their scale between the sides; dW, whose entries sum over every position, 1e-4
@@ -129,7 +145,8 @@ def main():
     ap.add_argument("--pool", action="store_true", help="time bag pooling (MedTokEmbedding.pooled) instead")
     ap.add_argument("--codebook-grad", action="store_true", help="time forward + backward with freeze_codebook=False instead")
     ap.add_argument("--sequence", type=int, default=0, metavar="H", help="time MedTokEmbedding.sequence against the torch composition instead")
-    ap.add_argument("--visits", type=int, default=100, help="--sequence: segments (visits) per batch row")
+    ap.add_argument("--segments", action="store_true", help="time MedTokEmbedding.pooled_segments (a row per visit) against the compositions instead")
+    ap.add_argument("--visits", type=int, default=100, help="--sequence / --segments: segments (visits) per batch row")
     ap.add_argument("--prefix", type=int, default=3, help="--sequence: rows in front of each batch row")
     ap.add_argument("--grad-form", action="store_true", help="with --project / --sequence: time grad_form='scatter' against 'dense' instead")
     ap.add_argument("--train-codebook", action="store_true", help="--project H --grad-form: with freeze_codebook=False")
@@ -172,6 +189,8 @@ def main():
         return codebook_grad_mode(args, dev, timed, inner_for, stats)
     if args.sequence:
         return sequence_mode(args, dev, timed, inner_for, stats)
+    if args.segments:
+        return segments_mode(args, dev, timed, inner_for, stats)
 
     result = {"tool": "tools/bench_embed.py", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
               "num_codes": args.codes, "positions": [args.batch, args.length], "slots": 4, "k": args.k, "padded_fraction": args.padded,
@@ -742,6 +761,133 @@ def sequence_mode(args, dev, timed, inner_for, stats):
         path = Path(args.out)
         whole = json.loads(path.read_text()) if path.exists() else {}
         whole["sequence"] = result
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(whole, indent=1) + "\n")
+    print(json.dumps(result))
+
+
+def segments_mode(args, dev, timed, inner_for, stats):
+    import torch
+    from medtok_amd import MedTokEmbedding, ops
+    from medtok_amd.vector_quantization_soft_one_new import VectorQuantizer
+    n_seg, batch, length = args.visits, args.batch, args.length
+    name = "reference"
+    d, n_e = SHAPES[name]["d"], SHAPES[name]["n_e"]
+    k, num_codes, n_pos, width = args.k, args.codes, batch * length, 4 * d
+    torch.manual_seed(0)
+    vq = VectorQuantizer(n_e, d, 0.25, 0.0, True, False, [d, d], k=k)
+    with torch.no_grad():
+        vq.codebook.weight.normal_()
+    vq = vq.to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(1)
+    sizes = [hi - lo for lo, hi in (vq._region(t) for t in TYPES)]
+    tokens = torch.stack([torch.randint(0, s, (num_codes, k), generator=gen, device=dev) for s in sizes], 1).contiguous()
+    weights = torch.softmax(torch.randn(num_codes, 4, k, generator=gen, device=dev), -1).contiguous()
+    module = MedTokEmbedding(vq, tokens, weights)
+    del tokens, weights
+    index = torch.randint(0, num_codes, (batch, length), generator=gen, device=dev)
+    u = torch.rand(batch, length, generator=gen, device=dev)
+    index[u < args.miss] = num_codes
+    mask = u > 1.0 - args.padded
+    index[mask] = 0                                         # (the reference's dataloader pads with code 0 under its code_mask)
+    ascending = torch.randint(0, n_seg, (batch, length), generator=gen, device=dev).sort(1).values      # visits in time order
+    shuffled = ascending.gather(1, torch.rand(batch, length, generator=gen, device=dev).argsort(1))
+    live = ~mask
+    row_base = (torch.arange(batch, device=dev) * n_seg).view(-1, 1)
+    result = {"tool": "tools/bench_embed.py --segments", "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0),
+              "chunk": ops.EMBED_POOL_CHUNK, "samples_of_at_least_ms": 50.0,
+              "expectation": "stated before measuring: pooled_segments is not slower than either composition by more than that composition's "
+                             "own run-to-run spread (median <= median + (max - min)); no speed-up is fixed in advance",
+              "shapes": {}}
+
+    def inner_for(fn):                                      # pool_mode's: samples of >= 50 ms (aimed at 65), the count corrected on samples
+        inner = 10                                          # of its own size (the first calls are slower than the steady ones)
+        for _ in range(6):
+            sample = timed(fn, inner) * inner
+            if sample >= 60.0 or inner >= 50000:
+                break
+            inner = max(inner + 1, min(50000, math.ceil(inner * 65.0 / max(sample, 1e-3))))
+        return inner
+
+    for case, seg in (("ascending", ascending), ("shuffled", shuffled)):
+        key = torch.where(live, row_base + seg, torch.full_like(seg, batch * n_seg)).reshape(-1)        # dead: one bin past the bags
+        outs = {}
+
+        def counts():
+            return torch.zeros(batch * n_seg + 1, device=dev).index_add_(0, key, live.reshape(-1).float())[:-1].view(batch, n_seg, 1)
+
+        def finish(sums):
+            c = counts()
+            return torch.where(c > 0, sums / c.clamp(min=1.0), torch.zeros_like(sums)), c.squeeze(-1) == 0
+
+        def pooled_segments():
+            with torch.no_grad():
+                outs["pooled_segments"] = module.pooled_segments(index, seg, n_seg, padding_mask=mask, validate=False)
+
+        def composition_segment_grad():
+            with torch.no_grad():
+                rows = module(index, padding_mask=mask, validate=False)
+                outs["composition_segment_grad"] = finish(ops.embed_sequence_segment_grad(rows, seg, n_seg, mask))
+
+        def composition_index_add():
+            with torch.no_grad():
+                rows = module(index, padding_mask=mask, validate=False)
+                sums = torch.zeros(batch * n_seg + 1, width, device=dev).index_add_(0, key, rows.view(-1, width))[:-1]
+                outs["composition_index_add"] = finish(sums.view(batch, n_seg, width))
+
+        sides = {"pooled_segments": pooled_segments, "composition_segment_grad": composition_segment_grad,
+                 "composition_index_add": composition_index_add}
+        for _ in range(args.warmup):
+            for fn in sides.values():
+                fn()
+        torch.cuda.synchronize()
+        got, empty = outs["pooled_segments"]
+        rel = {}
+        for s in ("composition_segment_grad", "composition_index_add"):
+            want, want_empty = outs[s]
+            rel[s] = float((got - want).abs().max() / want.abs().max().clamp(min=1e-30))
+            if rel[s] > 1e-5 or not torch.equal(empty, want_empty):
+                raise SystemExit(f"pooled_segments and {s} disagree at the timed size ({case}): rel {rel[s]:.3e}")
+        peak = {}
+        for s, fn in sides.items():
+            outs.clear()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            fn()
+            torch.cuda.synchronize()
+            peak[s] = torch.cuda.max_memory_allocated() - before
+        inner = {s: inner_for(fn) for s, fn in sides.items()}
+        ms = {s: [] for s in sides}
+        for _ in range(args.reps):                          # the sides alternate
+            for s, fn in sides.items():
+                ms[s].append(timed(fn, inner[s]))
+        with ops.ClockProbe(dev, max_seconds=10.0) as probe:
+            for _ in range(max(2, args.reps // 4)):
+                timed(pooled_segments, inner["pooled_segments"])
+        clock = probe.result()
+        st = {s: stats(v) for s, v in ms.items()}
+        seg_len = (~empty).sum().clamp(min=1)
+        entry = {"d": d, "n_e": n_e, "k": k, "num_codes": num_codes, "batch": batch, "length": length, "visits": n_seg, "width": width,
+                 "positions": n_pos, "live_positions": int(live.sum()), "padded_fraction": args.padded, "miss_fraction": args.miss,
+                 "normalize": False, "non_empty_segments": int((~empty).sum()), "mean_positions_per_non_empty_segment": float(live.sum() / seg_len),
+                 "rows_bytes": n_pos * width * 4, "out_bytes": batch * n_seg * width * 4,
+                 "workspace_bytes": int(ops._lib.load().medtok_embed_pool_segments_workspace_bytes(batch, length, n_seg, width)),
+                 "rel_vs": rel, "empty_masks_equal": True, "shortest_sample_ms": min(min(ms[s_]) * inner[s_] for s_ in sides),
+                 "clock_ghz": clock.get("ghz_mean"), "clock_region": "further pooled_segments samples right behind the timed region"}
+        for s in sides:
+            entry[s] = dict(st[s], calls_per_sample=inner[s], spread=(st[s]["ms_max"] - st[s]["ms_min"]) / st[s]["ms_median"], peak_bytes=peak[s],
+                            positions_per_s=n_pos / (st[s]["ms_median"] * 1e-3))
+        a = "pooled_segments"
+        for b in ("composition_segment_grad", "composition_index_add"):
+            entry[f"speedup_over_{b}"] = st[b]["ms_median"] / st[a]["ms_median"]
+            entry[f"pooled_segments_not_slower_within_spread_of_{b}"] = st[a]["ms_median"] <= st[b]["ms_median"] + (st[b]["ms_max"] - st[b]["ms_min"])
+            entry[f"peak_bytes_saved_vs_{b}"] = peak[b] - peak[a]
+        result["shapes"][case] = entry
+    if args.out:
+        path = Path(args.out)
+        whole = json.loads(path.read_text()) if path.exists() else {}
+        whole["segments"] = result
         path.parent.mkdir(parents=True, exist_ok=True)
         path.write_text(json.dumps(whole, indent=1) + "\n")
     print(json.dumps(result))
